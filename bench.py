@@ -9,6 +9,12 @@ T = 32 env steps on every one of the 4096 envs of the rank (simulator + fused po
 experience record + resets), critic passes + TD(lambda) + advantage normalisation, then 5 epochs x 8 minibatches of
 16384 samples with the gradient all-reduced over RCCL per minibatch (the reference's cadence).  Per-GPU work is fixed as
 N grows ("weak").  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the --steps iterations and reports the headline (env-steps/s, ms_per_step) with the
+figures of the timed iterations themselves (rollout share, episode statistics).  --full adds what takes runs of its own: the
+roofline of the fused post-step kernel (an eager rollout with event-timed launches, a rocprofv3 child, standalone replays),
+the other kernels of the step, the configs[3] stand-in launch and the CPU oracle baseline.
+--dump-outputs DIR writes what the last timed iteration computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -112,6 +118,35 @@ def post_step_in_rollout_by_the_profiler(workload, envs, steps=64, timeout_s=300
         shutil.rmtree(out, ignore_errors=True)
 
 
+DUMP_SAMPLE = 1 << 20          # elements kept of an array larger than this (fixed, seeded sample of flat indices)
+DUMP_LIMIT_BYTES = 64 << 20
+# the rollout's experience of the last iteration: what the update trained on (compute_time is wall-clock, so it is left out)
+DUMP_BUFFERS = ("obs", "action", "reward", "done", "a_logp", "tar_val", "adv")
+
+
+def dump_outputs(out_dir, agent, info):
+    """--dump-outputs: what the last timed iteration (DMPPOAgent._train_iter) hands its caller, as float32 / float64 .npy files -
+    info_<key>: the returned statistics (float64 scalars); state_<key>: the agent's state_dict after the update (policy / value
+    weights, normaliser statistics: what DMPPOAgent.save writes); buffer_<name>: the iteration's rollout experience [T, N, ...].
+    Arrays of more than DUMP_SAMPLE elements are stored as the elements at a fixed sample of flat indices (numpy seed 0 and the
+    array's shape decide it), so two builds run with the same arguments compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"info_" + k: torch.as_tensor(v, dtype=torch.float64) for k, v in info.items()}
+    arrays.update(("state_" + k, v) for k, v in agent.state_dict().items())
+    arrays.update(("buffer_" + k, agent._exp_buffer.get_data(k)) for k in DUMP_BUFFERS)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype in (np.float64, np.int64) else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT_BYTES, "--dump-outputs wrote {} bytes (limit {})".format(total, DUMP_LIMIT_BYTES)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) as a child torch.distributed.run job and
     relay rank 0's JSON line.  The parent makes no GPU call at all - the device count comes from the visibility variables or the KFD
@@ -191,7 +226,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--workload", default="boxes_64clips")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline of the fused post-step kernel, the other kernels of the step and "
+                         "the CPU oracle baseline (`roofline`, `kernels`, `cpu_baseline` in the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, fixed sample of large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle baseline")
     ap.add_argument("--no-profiler-child", action="store_true",
                     help="do not start the rocprofv3 child that times the post-step launch inside the rollout (roofline.us_per_launch then "
                          "comes from HIP events bound to the dispatch)")
@@ -204,6 +244,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="only start the ranks, rendezvous, barrier and MAX-reduce a timer (no GPU work, no metric): checks the launcher")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))          # `python bench.py --gpus N`: this process only starts the N ranks (no GPU call here)
@@ -221,7 +263,7 @@ def main():
         sys.exit("bench.py: --gpus {} needs {} visible GPUs, found {}".format(args.gpus, world, n_dev))
     dev = "cuda:{}".format(local_rank % max(n_dev, 1))     # (gloo rehearsal on a 1-GPU box: ranks share the device)
     torch.cuda.set_device(dev)
-    from parc_amd import _hip, workloads
+    from parc_amd import workloads
     from parc_amd.util import mp_util
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -272,7 +314,68 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = tt.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, agent, info)
+    full_figures = full_measurements(args, env, agent, dev, rank, world) if args.full else {}
 
+    replay_bound = None
+    try:
+        ml_ = env.get_dm_env()._motion_lib
+        w_ = ml_._motion_weights.double()
+        steps_ = torch.clamp(ml_._motion_lengths.double() * 0.5 / env._timestep, max=float(env._cfg.struct.episode_length) / env._timestep)
+        replay_bound = float((w_ * steps_).sum() / w_.sum())
+    except Exception:           # noqa: BLE001
+        replay_bound = None
+    if rank == 0:
+        total_env_steps = world * N * T * args.steps
+        out = {
+            "metric": "env-steps/sec (whole node), {} envs/GPU humanoid tracker at 1/2/4/8 MI355X".format(N),      # BASELINE.json's metric
+            "value": total_env_steps / elapsed,
+            "unit": "env-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            # weak: per-GPU work fixed; --scaling reference: the reference's rule, total samples per iteration fixed = "strong"
+            "scaling": "weak" if args.scaling == "weak" else "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "{} envs/GPU tracker on procgen box heightfields, 64 synthetic clips (BASELINE.json configs[2])".format(N)
+                       if args.workload == "boxes_64clips" else args.workload,
+                       "envs_per_gpu": N, "env_steps_per_bench_step": N * T, "rollout_steps": T, "update_epochs": agent._update_epochs,
+                       "minibatch": agent._batch_size * N, "sim_substeps": env._sim_steps * env._substeps, "parallelism": "dp{}".format(world),
+                       "scaling_rule": ("per-rank work fixed (T = 32, minibatch = 4 x envs): weak scaling" if args.scaling == "weak" else
+                                        "the reference's rule: T = ceil(32 / P) = {}, minibatch = ceil(4 / P) x envs = {} rows per rank "
+                                        "(base_agent.py:179-180, ppo_agent.py:27-29)".format(T, agent._batch_size * N)),
+                       "grad_allreduce": "per minibatch (reference cadence)" if args.grad_allreduce == "minibatch"
+                       else "per PPO epoch (parameter + momentum averaging)"},
+            **full_figures,
+            "rollout": ("one hipGraph replay per env step" + (", finished envs reset on the device inside the graph" if any(k[2] for k in agent._graphs)
+                                                               else " + eager reset of finished envs")) if agent._graphs else "eager",
+            "rollout_env_steps_per_s": world * N * T * args.steps / max(rollout_s[0], 1e-9),
+            "rollout_fraction_of_time": rollout_s[0] / elapsed,
+            "mean_episode_return": info["mean_return"] if info else None,
+            # SURVEY 8c: the return is reported absolute (no Isaac Gym run exists to compare with), next to the kinematic-replay upper
+            # bound: a character that sits on the reference pose earns reward 1 per step (tests/test_env_gpu.py::
+            # test_kinematic_replay_reward_upper_bound) from its uniformly drawn start phase to the end of its clip
+            "mean_episode_return_kinematic_upper_bound": replay_bound,
+            "mean_episode_length": info["mean_ep_len"] if info else None,
+        }
+        if args.full and not args.no_cpu_baseline and world == 1:       # (the CPU leg is a single-GPU datum: rank 0 at N=1 only)
+            out["cpu_baseline"] = cpu_baseline(env, clips, tiled)
+        print(json.dumps(out))
+    if world > 1:
+        barrier()
+        torch.distributed.destroy_process_group()
+
+
+def full_measurements(args, env, agent, dev, rank, world):
+    """--full: the roofline of the fused post-step kernel and the other kernels of the step, measured after the timed region
+    (every rank runs the eager rollout and the launch timing; rank 0 alone the per-kernel figures).  -> {"roofline", "kernels"}"""
+    from parc_amd import _hip, workloads
+    N, T = env.get_num_envs(), agent._steps_per_iter
     # dominant env kernel: the fused post-step launch (heightmap gather + reference pose + obs + reward + done).
     # Inside the timed region it runs as a node of the captured rollout graph, where a single node cannot be bracketed
     # with events; so (a) one extra EAGER rollout right after the region with an event pair around every launch, in the
@@ -454,41 +557,7 @@ def main():
             extra.append({"kernel": "policy / value MLP {} GEMM + bias + ReLU, {}x{}x{} (hipBLASLt fp32)".format(what, m_, k_, n_), "us_per_launch": us_g,
                           "bound": "mfma", "achieved_TFLOPs": tf, "peak_TFLOPs": MFMA_FP32_PEAK_TFLOPS, "frac_of_peak": tf / MFMA_FP32_PEAK_TFLOPS})
             del a_, w_, b_
-
-    replay_bound = None
-    try:
-        ml_ = env.get_dm_env()._motion_lib
-        w_ = ml_._motion_weights.double()
-        steps_ = torch.clamp(ml_._motion_lengths.double() * 0.5 / env._timestep, max=float(env._cfg.struct.episode_length) / env._timestep)
-        replay_bound = float((w_ * steps_).sum() / w_.sum())
-    except Exception:           # noqa: BLE001
-        replay_bound = None
-    if rank == 0:
-        total_env_steps = world * N * T * args.steps
-        out = {
-            "metric": "env-steps/sec (whole node), {} envs/GPU humanoid tracker at 1/2/4/8 MI355X".format(N),      # BASELINE.json's metric
-            "value": total_env_steps / elapsed,
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            # weak: per-GPU work fixed; --scaling reference: the reference's rule, total samples per iteration fixed = "strong"
-            "scaling": "weak" if args.scaling == "weak" else "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "{} envs/GPU tracker on procgen box heightfields, 64 synthetic clips (BASELINE.json configs[2])".format(N)
-                       if args.workload == "boxes_64clips" else args.workload,
-                       "envs_per_gpu": N, "env_steps_per_bench_step": N * T, "rollout_steps": T, "update_epochs": agent._update_epochs,
-                       "minibatch": agent._batch_size * N, "sim_substeps": env._sim_steps * env._substeps, "parallelism": "dp{}".format(world),
-                       "scaling_rule": ("per-rank work fixed (T = 32, minibatch = 4 x envs): weak scaling" if args.scaling == "weak" else
-                                        "the reference's rule: T = ceil(32 / P) = {}, minibatch = ceil(4 / P) x envs = {} rows per rank "
-                                        "(base_agent.py:179-180, ppo_agent.py:27-29)".format(T, agent._batch_size * N)),
-                       "grad_allreduce": "per minibatch (reference cadence)" if args.grad_allreduce == "minibatch"
-                       else "per PPO epoch (parameter + momentum averaging)"},
-            "roofline": {"kernel": "track_post_kernel (fused K5 heightmap gather + K3 K2 K4 K6-K10)", "bound": "hbm", "achieved": achieved,
+    return {"roofline": {"kernel": "track_post_kernel (fused K5 heightmap gather + K3 K2 K4 K6-K10)", "bound": "hbm", "achieved": achieved,
                          "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
                          "achieved_is": "ALGORITHMIC bytes per launch (SURVEY.md 8d: 13 592 B/env) / us_per_launch = the launch IN THE ROLLOUT "
                                         "STEP, where the product issues it (behind the simulator launch; its clip rows and destination lines "
@@ -517,24 +586,7 @@ def main():
                                              "(valu.frac_of_valu_issue_peak) is saturated - the launch is bound by the dependent chains of its pose waves "
                                              "(6 waves per workgroup, 70 VGPRs) and the drain of its row stores (DESIGN.md section 3)",
                          "valu": valu},
-            "rollout": ("one hipGraph replay per env step" + (", finished envs reset on the device inside the graph" if any(k[2] for k in agent._graphs)
-                                                               else " + eager reset of finished envs")) if agent._graphs else "eager",
-            "kernels": extra,
-            "rollout_env_steps_per_s": world * N * T * args.steps / max(rollout_s[0], 1e-9),
-            "rollout_fraction_of_time": rollout_s[0] / elapsed,
-            "mean_episode_return": info["mean_return"] if info else None,
-            # SURVEY 8c: the return is reported absolute (no Isaac Gym run exists to compare with), next to the kinematic-replay upper
-            # bound: a character that sits on the reference pose earns reward 1 per step (tests/test_env_gpu.py::
-            # test_kinematic_replay_reward_upper_bound) from its uniformly drawn start phase to the end of its clip
-            "mean_episode_return_kinematic_upper_bound": replay_bound,
-            "mean_episode_length": info["mean_ep_len"] if info else None,
-        }
-        if not args.no_cpu_baseline and world == 1:       # (the CPU leg is a single-GPU datum: rank 0 at N=1 only)
-            out["cpu_baseline"] = cpu_baseline(env, clips, tiled)
-        print(json.dumps(out))
-    if world > 1:
-        barrier()
-        torch.distributed.destroy_process_group()
+            "kernels": extra}
 
 
 if __name__ == "__main__":

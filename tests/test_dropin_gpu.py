@@ -118,6 +118,39 @@ def test_bench_two_ranks_from_a_plain_invocation():
         assert bad.returncode != 0 and bad.stdout.strip() == ""
 
 
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """A plain `python bench.py --gpus 1` times exactly --steps iterations and reports the headline figures only (`roofline`, `kernels`
+    and `cpu_baseline` are --full's); --dump-outputs writes what the last timed iteration computed as float32 / float64 .npy files within
+    64 MB, the same set of files with the same shapes on every run with the same arguments."""
+    import json
+    import subprocess
+    import sys
+    from conftest import REPO
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    lines, dumps = [], []
+    for i in range(2):
+        d = str(tmp_path / "dump{}".format(i))
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--envs", "64", "--steps", "2", "--warmup", "1",
+                              "--dump-outputs", d], capture_output=True, text=True, env=env, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(json.loads(out.stdout.strip().splitlines()[-1]))
+        dumps.append({f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    line = lines[0]
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "env-steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["value"] > 0
+    assert abs(line["value"] - 64 * 32 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "kernels", "cpu_baseline"} & set(line)
+    files = dumps[0]
+    assert {"info_mean_return.npy", "info_adv_std.npy", "buffer_obs.npy", "buffer_reward.npy", "buffer_adv.npy"} <= set(files)
+    assert any(f.startswith("state__model.") for f in files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["buffer_reward.npy"].shape == (32, 64) and float(files["info_mean_return.npy"]) == line["mean_episode_return"]
+    assert {f: a.shape for f, a in dumps[1].items()} == {f: a.shape for f, a in files.items()}
+
+
 def test_collectives_on_the_real_backend_with_one_rank():
     """RCCL itself (torch.distributed "nccl"), world size 1, the package's multi-process switch forced on inside the probe: every
     collective of the data-parallel path (bucketed asynchronous all-reduce of gradient views started from gradient callbacks, the
