@@ -67,6 +67,26 @@ int parc_sim_step_tick(void *stream, const parc_sim_model_t *model, parc_terrain
                        const float *action, const float *action_low, const float *action_high, int n_substeps, float h,
                        int32_t *timestep_buf, float *time_buf, float step_dt);
 
+/* Control modes of parc_sim_step_ctl, numbered like the reference's ControlMode enum (envs/ig_char_env.py:20-25). */
+#define PARC_SIM_CTL_PD 0       /* implicit position drive, targets = clamp(action): what parc_sim_step does */
+#define PARC_SIM_CTL_VEL 1      /* implicit velocity drive (stiffness ignored), velocity targets = clamp(action) */
+#define PARC_SIM_CTL_TORQUE 2   /* joint torque = clamp(action) */
+#define PARC_SIM_CTL_PD_EXP 3   /* explicit PD on the relative joint rotation, targets = action (unclamped), held per hold */
+#define PARC_SIM_CTL_PD_1D 4    /* explicit PD on the raw dof difference (1-D joints), targets = action (unclamped) */
+
+/* One control step in any control mode (envs/ig_char_env.py:378-420,489-504).  The n_substeps substeps form
+ * n_substeps / substeps_per_hold holds (one hold = one gym.simulate of substeps_per_hold PhysX substeps,
+ * envs/ig_env.py:830-837); the explicit modes (pd_exp, pd_1d) compute their torque at the start of every hold and keep
+ * it for the hold.  dof_torque [N,D] (optional; NULL for pd and vel) receives the torque of the last hold (torque,
+ * pd_exp, pd_1d).  timestep_buf / time_buf: both NULL, or both given (IGEnv._update_time as in parc_sim_step_tick).
+ * PARC_EINVAL for a mode out of range, n_substeps not a multiple of substeps_per_hold, only one of the clock buffers,
+ * or dof_torque given for pd / vel. */
+int parc_sim_step_ctl(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state,
+                      float *dof_state, float *rigid_body_state, float *contact_forces, const float *env_offsets,
+                      const float *action, const float *action_low, const float *action_high, int n_substeps, float h,
+                      int substeps_per_hold, int control_mode, float *dof_torque, int32_t *timestep_buf, float *time_buf,
+                      float step_dt);
+
 /* Recompute rigid_body_state (poses, velocities) from root_state / dof_state for the listed envs and zero
  * their contact forces: what the reference gets from refresh_rigid_body_state_tensor after a reset
  * (envs/ig_env.py:850-860).  env_ids int64 device pointer, NULL = all. */

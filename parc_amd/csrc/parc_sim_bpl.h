@@ -158,9 +158,11 @@ __device__ __forceinline__ ContactEval eval_contact(const parc_sim_model_t &m, c
 #define BPL_CC_SLOTS 8      // contacts per body kept in LDS between the impedance pass and the force report
 #define BPL_CC_FLOATS 11    // rc, nb, F0, cn, ct
 
+// MODE: PARC_SIM_CTL_*; th[3]: this joint's drive values in the modes other than pd (ctl_drive in parc_sim_core.h), unused by pd
+template <int MODE = PARC_SIM_CTL_PD>
 __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, const Lane &L, int b, int maxd,
                                         LState &x, float h, float cweight, float *lds /* [16][BPL_CONTRIB] of this env */,
-                                        float *cc /* [BPL_CC_SLOTS][BPL_CC_FLOATS] of this lane */) {
+                                        float *cc /* [BPL_CC_SLOTS][BPL_CC_FLOATS] of this lane */, const float *th = nullptr) {
     Kin k;
     kin_pass(L, b, maxd, x, k);
     const bool valid = L.depth >= 0;
@@ -258,7 +260,15 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
     for (int q = 0; q < 9; ++q) Ua.m[q] = Ul.m[q] = Dinv.m[q] = 0.f;
     // drive torque and the diagonal augmentation of D depend on this joint's own state only: once per substep, not per level
     float tau[3] = {0.f, 0.f, 0.f}, aug[3] = {0.f, 0.f, 0.f};
-    if (L.jt == PARC_JOINT_SPHERICAL) {
+    if constexpr (MODE != PARC_SIM_CTL_PD) {
+        if (L.jt == PARC_JOINT_SPHERICAL) {
+            const V3 e = q_to_exp(x.jq);
+            const float wv[3] = {x.jw.x, x.jw.y, x.jw.z}, ee[3] = {e.x, e.y, e.z};
+            ctl_drive<MODE>(m, L.d0, 3, ee, wv, th, h, tau, aug);
+        } else if (L.jt == PARC_JOINT_HINGE) {
+            ctl_drive<MODE>(m, L.d0, 1, &x.jang, &x.jw.x, th, h, tau, aug);
+        }
+    } else if (L.jt == PARC_JOINT_SPHERICAL) {
         V3 err = q_to_exp(qmul(qconj(x.jq), x.tq)) - h * x.jw;
         V3 e = q_to_exp(x.jq);
         const float ev[3] = {err.x, err.y, err.z}, wv[3] = {x.jw.x, x.jw.y, x.jw.z}, ee[3] = {e.x, e.y, e.z};
@@ -441,6 +451,8 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
     }
 }
 
+// CLAMP = false: the targets are the raw action (pd_exp / pd_1d, ig_char_env.py:501-504)
+template <bool CLAMP = true>
 __device__ __forceinline__ void load_lane_state(const parc_sim_model_t &m, const Lane &L, int b, const float *root_state, const float *dof_state,
                                                 const float *action, const float *act_lo, const float *act_hi, LState &x) {
     x.root_pos = ld(root_state);
@@ -460,13 +472,13 @@ __device__ __forceinline__ void load_lane_state(const parc_sim_model_t &m, const
         x.jw = v3(dof_state[2 * d0 + 1], dof_state[2 * (d0 + 1) + 1], dof_state[2 * (d0 + 2) + 1]);
         float t[3];
 #pragma unroll
-        for (int q = 0; q < 3; ++q) t[q] = clampf(action[d0 + q], act_lo[d0 + q], act_hi[d0 + q]);   // ig_char_env.py:490
+        for (int q = 0; q < 3; ++q) t[q] = CLAMP ? clampf(action[d0 + q], act_lo[d0 + q], act_hi[d0 + q]) : action[d0 + q];   // ig_char_env.py:490
         x.tq = exp_to_q(v3(t[0], t[1], t[2]));
     } else if (L.jt == PARC_JOINT_HINGE) {
         x.jang = dof_state[2 * d0];
         x.jw.x = dof_state[2 * d0 + 1];
         x.jq = exp_to_q(x.jang * L.ax);
-        x.tang = clampf(action[d0], act_lo[d0], act_hi[d0]);
+        x.tang = CLAMP ? clampf(action[d0], act_lo[d0], act_hi[d0]) : action[d0];
     }
 }
 
@@ -512,9 +524,13 @@ __device__ __forceinline__ void store_lane_state(const Lane &L, int b, int maxd,
 
 // The whole env step as seen by lane b of an env's 16-lane group: what sim_step_bpl_kernel runs (and what the host lane
 // emulation runs, lane by lane in lock step).  `lds`: BPL_G * BPL_CONTRIB floats shared by the group, `cc`: this lane's contact cache.
+// MODE: PARC_SIM_CTL_*; the modes other than pd run in holds of `hold` substeps and write the torque of the last hold to
+// dof_torque [D] (torque / pd_exp / pd_1d, optional): parc_sim_core.h env_step_ctl.  The joint's drive values stay in lane registers.
+template <int MODE = PARC_SIM_CTL_PD>
 __device__ __forceinline__ void step_lane(const parc_sim_model_t &m, const parc_terrain_t &ter, int b, float *root_state, float *dof_state,
                                           float *rigid_body_state, float *contact_forces, const float *env_offset, const float *action,
-                                          const float *act_lo, const float *act_hi, int n_sub, float h, float *lds, float *cc) {
+                                          const float *act_lo, const float *act_hi, int n_sub, float h, float *lds, float *cc, int hold = 1,
+                                          float *dof_torque = nullptr) {
     const Lane L = load_lane(m, b);
     int maxd = L.depth;
 #pragma unroll
@@ -523,11 +539,36 @@ __device__ __forceinline__ void step_lane(const parc_sim_model_t &m, const parc_
         maxd = other > maxd ? other : maxd;
     }
     LState x;
-    load_lane_state(m, L, b, root_state, dof_state, action, act_lo, act_hi, x);
+    load_lane_state<!ctl_explicit_pd<MODE>()>(m, L, b, root_state, dof_state, action, act_lo, act_hi, x);
     const V3 off = ld(env_offset);
     const float w = 1.0f / (float)n_sub;
-    for (int s = 0; s < n_sub; ++s) substep(m, ter, off, L, b, maxd, x, h, w, lds, cc);
-    store_lane_state(L, b, maxd, x, root_state, dof_state, rigid_body_state, contact_forces);
+    if constexpr (MODE == PARC_SIM_CTL_PD) {
+        for (int s = 0; s < n_sub; ++s) substep(m, ter, off, L, b, maxd, x, h, w, lds, cc);
+        store_lane_state(L, b, maxd, x, root_state, dof_state, rigid_body_state, contact_forces);
+    } else {
+        const int dd = L.jt == PARC_JOINT_SPHERICAL ? 3 : (L.jt == PARC_JOINT_HINGE ? 1 : 0);
+        float th[3] = {0.f, 0.f, 0.f};
+        if (MODE == PARC_SIM_CTL_VEL || MODE == PARC_SIM_CTL_TORQUE) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (q < dd) th[q] = clampf(action[L.d0 + q], act_lo[L.d0 + q], act_hi[L.d0 + q]);
+        }
+        int left = 0;      // substeps left in the current hold
+        for (int s = 0; s < n_sub; ++s) {
+            if (ctl_explicit_pd<MODE>() && left == 0) {
+                ctl_hold_torque<MODE>(m, L.jt, L.d0, L.ax, x.jq, x.jang, x.jw, x.tq, x.tang, th);
+                left = hold;
+            }
+            --left;
+            substep<MODE>(m, ter, off, L, b, maxd, x, h, w, lds, cc, th);
+        }
+        store_lane_state(L, b, maxd, x, root_state, dof_state, rigid_body_state, contact_forces);
+        if (dof_torque && MODE != PARC_SIM_CTL_VEL) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (q < dd) dof_torque[L.d0 + q] = th[q];
+        }
+    }
 }
 
 }  // namespace parc_sim_bpl

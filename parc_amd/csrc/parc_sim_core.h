@@ -642,8 +642,68 @@ PARC_HD void report_contacts(const parc_sim_model_t &m, const parc_terrain_t &te
 
 PARC_HD float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// ABA passes 2 and 3 + integration: one substep of length h.
-PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, State &x, Scratch &s, float h, float cweight) {
+// ---- control modes other than pd (PARC_SIM_CTL_*, envs/ig_char_env.py:115-131,378-420,489-504).  `th` holds one float per dof of
+// the joint: vel = the velocity target clamp(action), torque = the torque clamp(action), pd_exp / pd_1d = the torque of the current
+// hold (ctl_hold_torque).  Compile-time mode: the pd path keeps its own code (PARC_SIM_CTL_PD never reaches these).
+template <int MODE>
+PARC_HD constexpr bool ctl_explicit_pd() { return MODE == PARC_SIM_CTL_PD_EXP || MODE == PARC_SIM_CTL_PD_1D; }
+
+// Explicit PD torque of one joint at the start of a hold (IGCharEnv._calc_pd_exp_torque / _calc_pd_1d_torque, ig_char_env.py:399-420):
+// tau = clip(kp diff - kd qdot, -effort, +effort).  pd_exp: diff = exp-map of normalize(conj(q) q_tar) (compute_dof_vel,
+// anim/kin_char_model.py:552-581), projected on the axis for a hinge, so it wraps to (-pi, pi]; pd_1d: diff = tar - q, no wrap (a spherical
+// joint, which the env refuses, takes the difference of the exp-maps).  Unlike the pd drive, where effort <= 0 means "unlimited", this is
+// the reference's torch.clip: effort 0 gives torque 0.
+template <int MODE>
+PARC_HD void ctl_hold_torque(const parc_sim_model_t &m, int jt, int d0, V3 ax, Q4 jq, float jang, V3 jw, Q4 tq, float tang, float *th) {
+    if (jt == PARC_JOINT_SPHERICAL) {
+        const V3 diff = MODE == PARC_SIM_CTL_PD_EXP ? q_to_exp(qnormalize(qmul(qconj(jq), tq))) : q_to_exp(tq) - q_to_exp(jq);
+        const float dv[3] = {diff.x, diff.y, diff.z}, wv[3] = {jw.x, jw.y, jw.z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float lim = m.effort[d0 + k];
+            th[k] = clampf(m.kp[d0 + k] * dv[k] - m.kd[d0 + k] * wv[k], -lim, lim);
+        }
+    } else if (jt == PARC_JOINT_HINGE) {
+        const float diff = MODE == PARC_SIM_CTL_PD_EXP ? dot(ax, q_to_exp(qnormalize(qmul(qconj(jq), exp_to_q(tang * ax))))) : tang - jang;
+        const float lim = m.effort[d0];
+        th[0] = clampf(m.kp[d0] * diff - m.kd[d0] * jw.x, -lim, lim);
+    }
+}
+
+// Drive torque and diagonal augmentation of D for the dd dofs of one joint (ee: dof positions, wv: dof velocities).
+//   vel:    implicit velocity drive, tau = kd (v_tar - qdot), D += armature + h kd, scaled down like the pd drive when |tau| > effort > 0
+//   torque, pd_exp, pd_1d: explicit, tau = th, D += armature
+// plus the joint-limit springs of the pd path.
+template <int MODE>
+PARC_HD void ctl_drive(const parc_sim_model_t &m, int d0, int dd, const float *ee, const float *wv, const float *th, float h, float *tau,
+                       float *aug) {
+#pragma unroll
+    for (int k = 0; k < dd; ++k) {
+        if (MODE == PARC_SIM_CTL_VEL) {
+            const float kd = m.kd[d0 + k];
+            const float t = kd * (th[k] - wv[k]);
+            const float lim = m.effort[d0 + k];
+            const float sc = (lim > 0.f && fabsf(t) > lim) ? lim * p_rcp(fabsf(t)) : 1.0f;
+            tau[k] = sc * t;
+            aug[k] = m.armature[d0 + k] + sc * (h * kd);
+        } else {
+            tau[k] = th[k];
+            aug[k] = m.armature[d0 + k];
+        }
+        const float hi = m.limit_hi[d0 + k], lo = m.limit_lo[d0 + k];
+        const float over = ee[k] > hi ? ee[k] - hi : (ee[k] < lo ? ee[k] - lo : 0.f);
+        if (over != 0.f) {
+            tau[k] += -m.limit_kp * (over + h * wv[k]) - m.limit_kd * wv[k];
+            aug[k] += h * m.limit_kd + h * h * m.limit_kp;
+        }
+    }
+}
+
+// ABA passes 2 and 3 + integration: one substep of length h.  MODE: PARC_SIM_CTL_*; th [D]: the per-dof drive values of the modes other
+// than pd (ctl_drive), unused by pd.
+template <int MODE = PARC_SIM_CTL_PD>
+PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, State &x, Scratch &s, float h, float cweight,
+                     const float *th = nullptr) {
     const int B = m.num_bodies;
     pass1(m, ter, env_off, x, s, h);
     // ---- joint drives (implicit PD) and limits: tau and the diagonal augmentation of D
@@ -656,10 +716,15 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
         SI Ia = s.IA[i];
         SV pa = s.pA[i];
         if (jt == PARC_JOINT_SPHERICAL) {
+            float tau[3], aug[3];
+            if constexpr (MODE != PARC_SIM_CTL_PD) {
+                const V3 e = q_to_exp(x.jq[i]);
+                const float wv[3] = {x.jw[i].x, x.jw[i].y, x.jw[i].z}, ee[3] = {e.x, e.y, e.z};
+                ctl_drive<MODE>(m, d0, 3, ee, wv, th + d0, h, tau, aug);
+            } else {
             // predicted rotation error in the child frame: log(q^-1 q_target) - h w
             V3 err = q_to_exp(qmul(qconj(x.jq[i]), x.tq[i])) - h * x.jw[i];
             V3 e = q_to_exp(x.jq[i]);
-            float tau[3], aug[3];
             const float ev[3] = {err.x, err.y, err.z}, wv[3] = {x.jw[i].x, x.jw[i].y, x.jw[i].z}, ee[3] = {e.x, e.y, e.z};
             PARC_LOOP(5)
             for (int k = 0; k < 3; ++k) {
@@ -674,6 +739,7 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
                     tau[k] += -m.limit_kp * (over + h * wv[k]) - m.limit_kd * wv[k];
                     aug[k] += h * m.limit_kd + h * h * m.limit_kp;
                 }
+            }
             }
             M3 D = Ia.A;
             D.m[0] += aug[0]; D.m[4] += aug[1]; D.m[8] += aug[2];
@@ -694,17 +760,23 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
         } else if (jt == PARC_JOINT_HINGE) {
             V3 ax = ld(m.joint_axis[i]);
             float w = x.jw[i].x;
+            float tau, aug;
+            if constexpr (MODE != PARC_SIM_CTL_PD) {
+                const float ang = x.jang[i];
+                ctl_drive<MODE>(m, d0, 1, &ang, &w, th + d0, h, &tau, &aug);
+            } else {
             float kp = m.kp[d0], kd = m.kd[d0];
             float t = kp * (x.tang[i] - x.jang[i] - h * w) - kd * w;
             float lim = m.effort[d0];
             float sc = (lim > 0.f && fabsf(t) > lim) ? lim * p_rcp(fabsf(t)) : 1.0f;
-            float tau = sc * t;
-            float aug = m.armature[d0] + sc * (h * kd + h * h * kp);
+            tau = sc * t;
+            aug = m.armature[d0] + sc * (h * kd + h * h * kp);
             float ang = x.jang[i];
             float over = ang > m.limit_hi[d0] ? ang - m.limit_hi[d0] : (ang < m.limit_lo[d0] ? ang - m.limit_lo[d0] : 0.f);
             if (over != 0.f) {
                 tau += -m.limit_kp * (over + h * w) - m.limit_kd * w;
                 aug += h * m.limit_kd + h * h * m.limit_kp;
+            }
             }
             V3 ua = mul(Ia.A, ax), ul = mulT(Ia.B, ax);
             float D = dot(ax, ua) + aug;
@@ -810,6 +882,8 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
 }
 
 // ---- state <-> Isaac-Gym-layout tensors (envs/ig_env.py:764-780) -------------------------------------------
+// CLAMP = false: the targets are the raw action (pd_exp / pd_1d, ig_char_env.py:501-504)
+template <bool CLAMP = true>
 PARC_HD void load_state(const parc_sim_model_t &m, const float *root_state, const float *dof_state, const float *action,
                         const float *act_lo, const float *act_hi, State &x) {
     x.root_pos = ld(root_state);
@@ -831,13 +905,13 @@ PARC_HD void load_state(const parc_sim_model_t &m, const float *root_state, cons
             x.jw[i] = v3(dof_state[2 * d0 + 1], dof_state[2 * (d0 + 1) + 1], dof_state[2 * (d0 + 2) + 1]);
             float t[3];
             PARC_LOOP(8)
-            for (int k = 0; k < 3; ++k) t[k] = clampf(action[d0 + k], act_lo[d0 + k], act_hi[d0 + k]);   // ig_char_env.py:490
+            for (int k = 0; k < 3; ++k) t[k] = CLAMP ? clampf(action[d0 + k], act_lo[d0 + k], act_hi[d0 + k]) : action[d0 + k];   // ig_char_env.py:490
             x.tq[i] = exp_to_q(v3(t[0], t[1], t[2]));
         } else if (m.joint_type[i] == PARC_JOINT_HINGE) {
             x.jang[i] = dof_state[2 * d0];
             x.jw[i].x = dof_state[2 * d0 + 1];
             x.jq[i] = exp_to_q(x.jang[i] * ld(m.joint_axis[i]));
-            x.tang[i] = clampf(action[d0], act_lo[d0], act_hi[d0]);
+            x.tang[i] = CLAMP ? clampf(action[d0], act_lo[d0], act_hi[d0]) : action[d0];
         }
     }
 }
@@ -902,21 +976,48 @@ PARC_HD void publish_bodies(const parc_sim_model_t &m, const State &x, float *ri
     }
 }
 
-// One env step: `n_sub` substeps of length h with the PD targets held (envs/ig_env.py:830-837: sim_steps x substeps)
-PARC_HD void env_step(const parc_sim_model_t &m, const parc_terrain_t &ter, const float *env_offset, float *root_state, float *dof_state,
-                      float *rigid_body_state, float *contact_forces, const float *action, const float *act_lo, const float *act_hi,
-                      int n_sub, float h, Scratch &s) {
+// One env step in control mode MODE: `n_sub` substeps of length h (envs/ig_env.py:830-837: sim_steps x substeps), in holds of `hold`
+// substeps (one gym.simulate each).  pd / vel / torque keep their targets for the whole step; pd_exp / pd_1d recompute their torque at the
+// start of every hold (IGCharEnv._apply_forces before each gym.simulate, ig_char_env.py:378-395).  dof_torque [D] (optional): the
+// torque of the last hold (torque / pd_exp / pd_1d), what the reference leaves in _char_action_buffer.
+template <int MODE>
+PARC_HD void env_step_ctl(const parc_sim_model_t &m, const parc_terrain_t &ter, const float *env_offset, float *root_state, float *dof_state,
+                          float *rigid_body_state, float *contact_forces, const float *action, const float *act_lo, const float *act_hi,
+                          int n_sub, float h, Scratch &s, int hold, float *dof_torque) {
     State x;
 #if defined(PARC_SIM_FILL_STATE)     // host test builds: start from a known byte pattern (oracle/Makefile `poison`)
     memset((void *)&x, PARC_SIM_FILL_STATE, sizeof x);
 #endif
-    load_state(m, root_state, dof_state, action, act_lo, act_hi, x);
+    load_state<!ctl_explicit_pd<MODE>()>(m, root_state, dof_state, action, act_lo, act_hi, x);
+    float th[PARC_SIM_MAX_DOFS];
+    for (int d = 0; d < m.dof_size; ++d)
+        th[d] = (MODE == PARC_SIM_CTL_VEL || MODE == PARC_SIM_CTL_TORQUE) ? clampf(action[d], act_lo[d], act_hi[d]) : 0.f;
     V3 off = ld(env_offset);
     const float w = 1.0f / (float)n_sub;
+    int left = 0;          // substeps left in the current hold
     PARC_LOOP(11)
-    for (int k = 0; k < n_sub; ++k) substep(m, ter, off, x, s, h, w);
+    for (int k = 0; k < n_sub; ++k) {
+        if (ctl_explicit_pd<MODE>() && left == 0) {
+            for (int i = 1; i < m.num_bodies; ++i)
+                ctl_hold_torque<MODE>(m, m.joint_type[i], m.dof_idx[i], ld(m.joint_axis[i]), x.jq[i], x.jang[i], x.jw[i], x.tq[i], x.tang[i],
+                                      th + m.dof_idx[i]);
+            left = hold;
+        }
+        --left;
+        substep<MODE>(m, ter, off, x, s, h, w, th);
+    }
     store_state(m, x, s, root_state, dof_state, rigid_body_state, contact_forces);
     publish_bodies(m, x, rigid_body_state, contact_forces);
+    if (dof_torque && MODE != PARC_SIM_CTL_PD && MODE != PARC_SIM_CTL_VEL)
+        for (int d = 0; d < m.dof_size; ++d) dof_torque[d] = th[d];
+}
+
+// One env step with the PD targets held (the pd control mode)
+PARC_HD void env_step(const parc_sim_model_t &m, const parc_terrain_t &ter, const float *env_offset, float *root_state, float *dof_state,
+                      float *rigid_body_state, float *contact_forces, const float *action, const float *act_lo, const float *act_hi,
+                      int n_sub, float h, Scratch &s) {
+    env_step_ctl<PARC_SIM_CTL_PD>(m, ter, env_offset, root_state, dof_state, rigid_body_state, contact_forces, action, act_lo, act_hi, n_sub, h,
+                                  s, 1, nullptr);
 }
 
 }  // namespace parc_sim

@@ -24,7 +24,8 @@ import torch
 from ... import _hip
 from ...anim import kin_char_model
 from ...gym_spaces import Box
-from ...sim_model import SimModel, action_bounds_pd
+from ... import _hip_sim
+from ...sim_model import SimModel, action_bounds, check_control_mode
 from ...tracker_core import TrackerConfig, TrackerCore
 from ...util import geom_util, terrain_util, torch_util
 from .. import base_env
@@ -80,9 +81,12 @@ class IGParkourEnv(base_env.BaseEnv):
         self._kin_char_model = kin_char_model.KinCharModel(device)
         self._kin_char_model.load_char_file(env_config["char_file"])
         km = self._kin_char_model
-        assert env_config["control_mode"] == "pd", "only the PD control mode of the tracker config is implemented"
+        # control mode (ig_char_env.py:20-25,92-135,229-253,262-274): pd / vel / torque / pd_exp / pd_1d, fixed at construction
+        self._control_mode = env_config["control_mode"]
+        check_control_mode(km, self._control_mode)
+        self._ctl = _hip_sim.CONTROL_MODES[self._control_mode]
         self._sim_model = SimModel(km)
-        low, high = action_bounds_pd(km)
+        low, high = action_bounds(km, self._sim_model, self._control_mode)
         self._action_space = Box(low=low.astype(np.float32), high=high.astype(np.float32))
         self._action_bound_low = torch.tensor(low, dtype=torch.float32, device=device)
         self._action_bound_high = torch.tensor(high, dtype=torch.float32, device=device)
@@ -175,6 +179,9 @@ class IGParkourEnv(base_env.BaseEnv):
         self._contact_body_ids = torch.tensor(self._cfg.contact_body_ids, dtype=torch.long, device=self._device)
         self._num_rbs = B
         self._action_buffer = torch.zeros((N, D), dtype=torch.float32, device=self._device)
+        # torque / pd_exp / pd_1d: the joint torque of the last hold of the latest step (what the reference leaves in _char_action_buffer,
+        # ig_char_env.py:378-395)
+        self._dof_torque = torch.zeros((N, D), dtype=torch.float32, device=self._device) if self._ctl in (2, 3, 4) else None
         init_pose = env_config.get("init_pose", None)
         self._init_pose = torch.tensor(init_pose if init_pose is not None else [0.0] * (6 + D), dtype=torch.float32, device=self._device)
 
@@ -206,6 +213,13 @@ class IGParkourEnv(base_env.BaseEnv):
     # ------------------------------------------------------------------ env API (envs/base_env.py, envs/ig_env.py:51-98)
     def get_num_envs(self):
         return self._num_envs
+
+    def get_control_mode(self):
+        return self._control_mode
+
+    def get_dof_torque(self):
+        """[N, D] joint torque of the last hold of the latest step (torque / pd_exp / pd_1d control modes), else None"""
+        return self._dof_torque
 
     def get_reward_bounds(self):
         return (0.0, 1.0)
@@ -549,12 +563,15 @@ class IGParkourEnv(base_env.BaseEnv):
             return self._step_sub_envs(act)
         # _pre_physics_step + _physics_step: PD targets = clipped action, sim_steps x substeps at h; _update_time (ig_env.py:862-865:
         # timestep += 1, time = timestep * dt) rides in the same launch
-        L = _hip.lib()
-        sim_args = (_hip.stream(), self._sim_model.device_ptr(self._device), c._terrain_struct, self._num_envs, _hip.ptr(c.root_state),
-                    _hip.ptr(c.dof_state), _hip.ptr(c.rigid_body_state), _hip.ptr(c.contact_forces), _hip.ptr(c.env_offsets), _hip.ptr(act),
-                    _hip.ptr(self._action_bound_low), _hip.ptr(self._action_bound_high), self._sim_steps * self._substeps, self._sim_h)
-        _hip.check(L.parc_sim_step_tick(*sim_args, _hip.ptr(self._timestep_buf), _hip.ptr(self._time_buf), float(self._timestep)),
-                   "parc_sim_step_tick")
+        if self._ctl != _hip_sim.CONTROL_MODES["pd"]:
+            self._sim_rows(act, 0, self._num_envs, c._terrain_struct)
+        else:
+            L = _hip.lib()
+            sim_args = (_hip.stream(), self._sim_model.device_ptr(self._device), c._terrain_struct, self._num_envs, _hip.ptr(c.root_state),
+                        _hip.ptr(c.dof_state), _hip.ptr(c.rigid_body_state), _hip.ptr(c.contact_forces), _hip.ptr(c.env_offsets), _hip.ptr(act),
+                        _hip.ptr(self._action_bound_low), _hip.ptr(self._action_bound_high), self._sim_steps * self._substeps, self._sim_h)
+            _hip.check(L.parc_sim_step_tick(*sim_args, _hip.ptr(self._timestep_buf), _hip.ptr(self._time_buf), float(self._timestep)),
+                       "parc_sim_step_tick")
         # _update_misc (incl. the xy target resample) / _update_observations / _update_reward / _update_done in one launch
         self._draw_step_uniforms()      # all uniforms of this step and of the restarts that follow it (tracker_core.rand_pool)
         # (the reference STATE - ref_* buffers - rides in the fail-rate launch below: nothing in the fused launch reads it)
@@ -574,6 +591,15 @@ class IGParkourEnv(base_env.BaseEnv):
         c = self._core
         B, D = self._cfg.num_bodies, self._cfg.dof_size
         p = _hip.ptr
+        if self._ctl != _hip_sim.CONTROL_MODES["pd"]:
+            # the other control modes: holds of `substeps` (one gym.simulate each); pd_exp / pd_1d ignore the bounds (unclipped targets)
+            _hip.check(_hip.lib().parc_sim_step_ctl(_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]),
+                                                    p(c.dof_state[e0 * D:]), p(c.rigid_body_state[e0 * B:]), p(c.contact_forces[e0 * B:]),
+                                                    p(c.env_offsets[e0:]), p(act[e0:]), p(self._action_bound_low), p(self._action_bound_high),
+                                                    self._sim_steps * self._substeps, self._sim_h, self._substeps, self._ctl,
+                                                    p(self._dof_torque[e0:]) if self._dof_torque is not None else None,
+                                                    p(self._timestep_buf[e0:]), p(self._time_buf[e0:]), float(self._timestep)), "parc_sim_step_ctl")
+            return
         _hip.check(_hip.lib().parc_sim_step_tick(_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]),
                                                  p(c.dof_state[e0 * D:]), p(c.rigid_body_state[e0 * B:]), p(c.contact_forces[e0 * B:]),
                                                  p(c.env_offsets[e0:]), p(act[e0:]), p(self._action_bound_low), p(self._action_bound_high),

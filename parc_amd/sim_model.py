@@ -259,3 +259,29 @@ def action_bounds_pd(kin_char_model):
             scale = 0.7 * (jh - jl)
             low[d0:d0 + dd], high[d0:d0 + dd] = mid - scale, mid + scale
     return low, high
+
+
+CONTROL_MODES = ("pd", "vel", "torque", "pd_exp", "pd_1d")      # the reference's ControlMode enum, in its order (ig_char_env.py:20-25)
+
+
+def check_control_mode(kin_char_model, control_mode):
+    """The reference's checks of the `control_mode` switch: a known mode (ig_char_env.py:92), and pd_1d only on a character whose joints
+    are all 1-D (_build_pd_exp_tensors :246-251)."""
+    assert control_mode in CONTROL_MODES, "Unsupported control mode: {}".format(control_mode)
+    if control_mode == "pd_1d":
+        for j in range(1, kin_char_model.get_num_joints()):
+            assert kin_char_model.get_joint(j).get_dof_dim() == 1, "pd_1d only supports 1D joints"
+
+
+def action_bounds(kin_char_model, sim_model, control_mode):
+    """Action bounds of a control mode (reference: IGCharEnv._build_action_space, envs/ig_char_env.py:255-274): pd / pd_exp / pd_1d the
+    joint-range bounds of action_bounds_pd, vel +-2 pi (_build_action_bounds_vel :350-354), torque +-motor effort, i.e. the MJCF motor
+    gears (_build_action_bounds_torque :356-363)."""
+    D = kin_char_model.get_dof_size()
+    if control_mode == "vel":
+        return -2.0 * np.pi * np.ones(D), 2.0 * np.pi * np.ones(D)
+    if control_mode == "torque":
+        effort = np.array([sim_model.struct.effort[d] for d in range(D)], dtype=np.float64)
+        return -effort, effort
+    assert control_mode in ("pd", "pd_exp", "pd_1d"), control_mode
+    return action_bounds_pd(kin_char_model)

@@ -1,0 +1,201 @@
+"""The control modes on the DEVICE: the checks of tests/test_control_modes.py on sim_step_bpl_ctl_kernel through parc_sim_step_ctl, the
+device against the host builds, parc_sim_step_ctl(pd) against parc_sim_step bit for bit, and the env in the vel / torque / pd_exp modes
+(eager and captured rollouts, mixed sub-env rows)."""
+import copy
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import REPO
+
+sys.path.insert(0, os.path.join(REPO, "tests", "tools"))
+import sim_ctl  # noqa: E402
+import test_control_modes as cm  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def hostlib(tmp_path_factory):
+    return sim_ctl.build_host(str(tmp_path_factory.mktemp("sim_ctl")))
+
+
+@pytest.fixture(scope="module")
+def humanoid():
+    return sim_ctl.humanoid_struct()
+
+
+def test_pd_exp_torque_matches_the_reference_on_the_device(humanoid):
+    cm.check_pd_exp_torque_matches_the_reference(humanoid, "device", None)
+
+
+def test_hinge_chain_matches_the_reference_on_the_device(tmp_path):
+    cm.check_hinge_chain_matches_the_reference("device", None, tmp_path)
+
+
+def test_action_bounds_and_apply_action_on_the_device(humanoid):
+    cm.check_action_bounds_and_apply_action(humanoid, "device", None)
+
+
+def test_torque_mode_closed_form_on_the_device(humanoid):
+    cm.check_torque_mode_closed_form(humanoid, "device", None)
+
+
+@pytest.mark.parametrize("joint", [1, 2])
+def test_vel_mode_closed_form_on_the_device(humanoid, joint):
+    cm.check_vel_mode_closed_form(humanoid, "device", None, joint)
+
+
+def test_explicit_pd_closed_form_on_the_device(humanoid):
+    cm.check_explicit_pd_closed_form(humanoid, "device", None)
+
+
+def test_torque_mode_conserves_momentum_on_the_device(humanoid):
+    cm.check_torque_mode_conserves_momentum(humanoid, "device", None)
+
+
+def test_device_matches_the_host_build_in_every_mode(humanoid, hostlib):
+    """One step of every mode from perturbed free-flight states: the device kernel and the host build of the same header agree: the
+    torque of the hold to 1e-5 relative (cm.close), the state to 2e-4."""
+    _, sm = humanoid
+    rng = np.random.default_rng(11)
+    n = 32
+    dof = rng.normal(0.0, 0.3, (n, 28)).astype(np.float32)
+    vel = rng.normal(0.0, 1.0, (n, 28)).astype(np.float32)
+    act = rng.normal(0.0, 0.5, (n, 28)).astype(np.float32)
+    for mode in sim_ctl.MODES:
+        out = []
+        for variant in ("bpl", "device"):
+            sim = sim_ctl.CtlSim(copy.deepcopy(sm.struct), n, variant, lib=hostlib)
+            sim.m.gravity = 0.0
+            sim.root_state[:, 2] = 3.0
+            sim.dof_state[..., 0], sim.dof_state[..., 1] = dof, vel
+            tq = sim.step(act, mode, n_sub=2, hold=2)
+            out.append((sim.dof_state.copy(), tq))
+        # (the state after two substeps: the device's 1-ulp sqrt / reciprocal and polynomial sin / atan against libm, ~1e-4 of a rate)
+        np.testing.assert_allclose(out[1][0], out[0][0], rtol=2e-4, atol=2e-4, err_msg=mode)
+        if out[0][1] is not None:
+            kp = np.array([sm.struct.kp[d] for d in range(28)])
+            ok, where, vals = cm.close(out[1][1], out[0][1], kp)
+            assert ok, (mode, where, vals)
+
+
+def test_step_ctl_pd_is_bitwise_parc_sim_step():
+    """parc_sim_step_ctl with PARC_SIM_CTL_PD runs the pd kernel itself: 10 steps of a 1024-env humanoid state are bit-identical."""
+    from parc_amd import _hip, workloads
+    N = 1024
+    env, _, _ = workloads.build_env("boxes_64clips", N, DEV, seed=0)
+    env.reset()
+    c = env._core
+    torch.manual_seed(0)
+    acts = [env._ref_dof_pos.clone() + 0.1 * torch.randn_like(env._ref_dof_pos) for _ in range(10)]
+    start = [t.clone() for t in (c.root_state, c.dof_state, c.rigid_body_state, c.contact_forces)]
+    res = []
+    for use_ctl in (False, True):
+        for t, s in zip((c.root_state, c.dof_state, c.rigid_body_state, c.contact_forces), start):
+            t.copy_(s)
+        for a in acts:
+            args = (_hip.stream(), env._sim_model.device_ptr(DEV), c._terrain_struct, N, _hip.ptr(c.root_state), _hip.ptr(c.dof_state),
+                    _hip.ptr(c.rigid_body_state), _hip.ptr(c.contact_forces), _hip.ptr(c.env_offsets), _hip.ptr(a),
+                    _hip.ptr(env._action_bound_low), _hip.ptr(env._action_bound_high), env._sim_steps * env._substeps, env._sim_h)
+            rc = _hip.lib().parc_sim_step_ctl(*args, env._substeps, 0, None, None, None, 0.0) if use_ctl else _hip.lib().parc_sim_step(*args)
+            _hip.check(rc, "step")
+        torch.cuda.synchronize()
+        res.append([t.clone() for t in (c.root_state, c.dof_state, c.rigid_body_state, c.contact_forces)])
+    for a, b in zip(*res):
+        assert torch.equal(a, b)
+    assert not torch.equal(res[0][1], start[1])
+
+
+@pytest.mark.parametrize("mode", ["vel", "torque", "pd_exp"])
+def test_env_steps_in_the_mode(mode):
+    """boxes_64clips at 1024 envs with control_mode = mode: the action space of the mode, 100 steps of uniform random in-bound actions
+    stay finite, the torque of the explicit modes stays within +-effort."""
+    from parc_amd import workloads
+    from parc_amd.sim_model import action_bounds
+    N = 1024
+    env, _, _ = workloads.build_env("boxes_64clips", N, DEV, seed=1, env_overrides={"control_mode": mode})
+    assert env.get_control_mode() == mode
+    lo, hi = action_bounds(env._kin_char_model, env._sim_model, mode)
+    np.testing.assert_array_equal(env.get_action_space().low, lo.astype(np.float32))
+    np.testing.assert_array_equal(env.get_action_space().high, hi.astype(np.float32))
+    eff = torch.tensor([env._sim_model.struct.effort[d] for d in range(28)], device=DEV)
+    if mode == "vel":
+        assert np.allclose(hi, 2 * np.pi)
+    if mode == "torque":
+        assert torch.equal(env._action_bound_high, eff)
+    low, high = env._action_bound_low, env._action_bound_high
+    env.reset()
+    gen = torch.Generator(device=DEV).manual_seed(0)
+    for _ in range(100):
+        a = low + (high - low) * torch.rand((N, 28), device=DEV, generator=gen)
+        obs, r, done, info = env.step(a)
+        assert torch.isfinite(obs).all() and torch.isfinite(r).all()
+        env.reset(torch.nonzero(done != 0).flatten()) if (done != 0).any() else None
+        if mode != "vel":
+            tq = env.get_dof_torque()
+            assert torch.isfinite(tq).all() and (tq.abs() <= eff + 1e-4).all()
+    assert torch.isfinite(env._core.dof_state).all()
+    if mode == "vel":
+        assert env.get_dof_torque() is None
+
+
+def test_graph_rollout_in_pd_exp_writes_the_same_rows_as_the_eager_rollout():
+    """(the pattern of test_learner_gpu.test_graph_rollout_writes_the_same_rows_as_the_eager_rollout, control_mode pd_exp) the captured
+    training step and the eager one fill the experience rows consistently."""
+    from parc_amd import workloads
+    from parc_amd.learning.dm_ppo_agent import AgentMode
+    torch.manual_seed(0)
+    env, _, _ = workloads.build_env("flat_1clip", 64, DEV, seed=0, env_overrides={"control_mode": "pd_exp"})
+    agent = workloads.build_agent(env, DEV, steps_per_iter=8, update_epochs=1, batch_size=2)
+    assert agent._device_tick()
+    agent._curr_obs, agent._curr_info = env.reset()
+    agent._init_train()
+    for it in range(3):
+        if it < 2:
+            info = agent._train_iter()
+            assert np.isfinite(info["critic_loss"].item())
+        else:
+            agent._exp_buffer.reset()
+            agent.eval()
+            agent.set_mode(AgentMode.TRAIN)
+            agent._rollout_train(agent._steps_per_iter)
+            assert agent._graphs
+        eb = agent._exp_buffer
+        ts = eb.get_data("timestep").cpu().numpy()
+        ep = eb.get_data("ep_num").cpu().numpy()
+        assert (eb.get_data("env_id").cpu().numpy() == np.arange(64)[None, :]).all()
+        d_ts, d_ep = np.diff(ts, axis=0), np.diff(ep, axis=0)
+        done = eb.get_data("done").cpu().numpy()[:-1] != 0
+        assert np.all(np.where(done, ts[1:] == 1, d_ts == 1)) and np.all(np.where(done, d_ep == 1, d_ep == 0))
+        obs, nxt = eb.get_data("obs"), eb.get_data("next_obs")
+        keep = ~torch.tensor(done, device=DEV)
+        assert torch.equal(obs[1:][keep], nxt[:-1][keep])
+        assert torch.isfinite(eb.get_data("action")).all() and torch.isfinite(obs).all()
+    assert torch.isfinite(env.get_dof_torque()).all() and env.get_dof_torque().abs().sum() > 0
+
+
+def test_mixed_rows_step_in_pd_exp():
+    """fraction_dm_envs < 1 (dataset and generator rows, one launch per sub-env): pd_exp steps both, the torque rows of both are written."""
+    from parc_amd import workloads
+    from test_mgdm_gpu import WalkGenerator
+    N = 64
+    mg_cfg = {"plan_length": 0.5, "ddim_stride": 50, "max_replans": 3, "cfg_scale": 0.7, "target_dist_max": 4.0, "target_dist_min": 1.0,
+              "target_dur_max": 2.0, "target_dur_min": 1.0, "target_heading_scale": 0.5, "generator": WalkGenerator(),
+              "heightmap": {"horizontal_scale": 0.4, "sq_m_per_env": 0.5, "safety_region": 3.0, "num_segments": 6, "platform_heights": [0.0]}}
+    env, _, _ = workloads.build_env("boxes_64clips", N, DEV, seed=3, env_overrides={"fraction_dm_envs": 0.5, "mgdm": mg_cfg, "control_mode": "pd_exp"})
+    n_dm = env._num_dm_envs
+    assert env.has_mgdm_envs() and n_dm == 32
+    env.reset()
+    env.get_dof_torque().fill_(float("nan"))
+    for _ in range(20):
+        obs, r, done, info = env.step(env._ref_dof_pos.clone())
+        assert torch.isfinite(obs).all() and torch.isfinite(r).all()
+        env.reset(torch.nonzero(done != 0).flatten()) if (done != 0).any() else None
+    tq = env.get_dof_torque()
+    assert torch.isfinite(tq).all()
+    assert tq[:n_dm].abs().sum() > 0 and tq[n_dm:].abs().sum() > 0

@@ -1,0 +1,36 @@
+// HOST build of the simulator core (parc_amd/csrc/parc_sim_core.h) in every control mode -- TEST INFRASTRUCTURE ONLY
+// (tests/test_control_modes.py builds it into a temporary directory with the host compiler).  The core's host entry points come
+// with the include; this adds the step with a control mode, a hold length and the dof torque output of parc_sim_step_ctl.
+#include "../../oracle/sim_host.cpp"
+
+namespace {
+template <int MODE>
+void step_core(const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state, float *dof_state, float *rigid_body_state,
+               float *contact_forces, const float *env_offsets, const float *action, const float *action_low, const float *action_high,
+               int n_substeps, float h, int hold, float *dof_torque) {
+    const int B = model->num_bodies, D = model->dof_size;
+    for (int e = 0; e < n_envs; ++e) {
+        parc_sim::Scratch s;
+        if (g_fill >= 0) memset((void *)&s, g_fill, sizeof s);
+        parc_sim::env_step_ctl<MODE>(*model, terrain, env_offsets + 3 * (size_t)e, root_state + 13 * (size_t)e, dof_state + 2 * (size_t)D * e,
+                                     rigid_body_state + 13 * (size_t)B * e, contact_forces + 3 * (size_t)B * e, action + (size_t)D * e,
+                                     action_low, action_high, n_substeps, h, s, hold, dof_torque ? dof_torque + (size_t)D * e : nullptr);
+    }
+}
+}  // namespace
+
+extern "C" int sim_ctl_host_step(const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state, float *dof_state,
+                                 float *rigid_body_state, float *contact_forces, const float *env_offsets, const float *action,
+                                 const float *action_low, const float *action_high, int n_substeps, float h, int hold, int mode,
+                                 float *dof_torque) {
+    if (hold <= 0 || n_substeps % hold != 0) return PARC_EINVAL;
+    switch (mode) {
+    case PARC_SIM_CTL_PD: step_core<PARC_SIM_CTL_PD>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
+    case PARC_SIM_CTL_VEL: step_core<PARC_SIM_CTL_VEL>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
+    case PARC_SIM_CTL_TORQUE: step_core<PARC_SIM_CTL_TORQUE>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
+    case PARC_SIM_CTL_PD_EXP: step_core<PARC_SIM_CTL_PD_EXP>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
+    case PARC_SIM_CTL_PD_1D: step_core<PARC_SIM_CTL_PD_1D>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
+    default: return PARC_EINVAL;
+    }
+    return 0;
+}
