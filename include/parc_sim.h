@@ -87,6 +87,61 @@ int parc_sim_step_ctl(void *stream, const parc_sim_model_t *model, parc_terrain_
                       int substeps_per_hold, int control_mode, float *dof_torque, int32_t *timestep_buf, float *time_buf,
                       float step_dt);
 
+/* Per-env physics parameters of parc_sim_step_phys: one row per env, N rows on the device.  The first five fields replace the model
+ * struct's constants of the same name for that env; the scales multiply what the model holds.
+ *   mass_scale      every link's mass and inertia (not armature, gains or effort)
+ *   kp_scale/kd_scale  the drive gains m.kp / m.kd in every control mode (not the limit springs)
+ *   push_force      world-frame force at the root link's centre of mass, applied in every substep while push_steps_left > 0;
+ *                   the step decrements push_steps_left once per launch (= one control step)
+ *   push_next_in    control steps until the sampler (parc_phys_rand) draws the next push; the step does not read it */
+typedef struct {
+    float gravity;
+    float friction_mu;
+    float contact_kn, contact_cn, contact_ct;
+    float mass_scale;
+    float kp_scale, kd_scale;
+    float push_force[3];
+    int32_t push_steps_left;
+    int32_t push_next_in;
+    int32_t _pad[3];                               /* rows are 64 bytes */
+} parc_sim_env_params_t;
+
+/* parc_sim_step_ctl with the per-env table env_params [N] (a DEVICE pointer): every control mode, pd included, runs
+ * sim_step_bpl_phys_kernel<MODE>.  A table filled with the model's own constants, scales 1 and no push reproduces parc_sim_step /
+ * parc_sim_step_ctl bit for bit.  PARC_EINVAL for what parc_sim_step_ctl refuses, for a NULL table, and for a row with a non-finite
+ * or non-positive mass_scale, contact_kn or kp_scale, a negative (or NaN) friction_mu, contact_cn, contact_ct or kd_scale, a
+ * non-finite gravity or push_force, or a negative push_steps_left.  The rows are checked by a small launch over the table in front
+ * of the step whose one-word verdict the call waits for; while `stream` is being captured into a hipGraph nothing can be waited
+ * for, so there the check is skipped and the table is the caller's responsibility (the env validates what it writes). */
+int parc_sim_step_phys(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state,
+                       float *dof_state, float *rigid_body_state, float *contact_forces, const float *env_offsets,
+                       const float *action, const float *action_low, const float *action_high, int n_substeps, float h,
+                       int substeps_per_hold, parc_sim_env_params_t *env_params, int control_mode, float *dof_torque,
+                       int32_t *timestep_buf, float *time_buf, float step_dt);
+
+/* The verdict alone: PARC_OK, or PARC_EINVAL if any of the n_envs rows breaks the rules above (waits for the stream). */
+int parc_sim_env_params_check(void *stream, const parc_sim_env_params_t *env_params, int n_envs);
+
+/* Ranges of the device-side sampler, [lo, hi] each; lo == hi fixes the value.  contact_kn / contact_cn / contact_ct / mass_scale are
+ * drawn log-uniformly, the others uniformly.  Push: every push_interval (control steps, uniform integer in [lo, hi]) a horizontal
+ * force of magnitude in push_force, uniform direction, for push_duration control steps; push_interval[1] <= 0 = no pushes. */
+typedef struct {
+    float gravity[2], friction_mu[2], contact_kn[2], contact_cn[2], contact_ct[2], mass_scale[2], kp_scale[2], kd_scale[2];
+    float push_force[2];
+    int32_t push_interval[2], push_duration[2];
+    int32_t push_tick;                             /* != 0: this launch counts the push schedule down (one control step) */
+    uint32_t field_mask;                           /* bit k set: field k (order above, gravity = bit 0 .. kd_scale = bit 7) is redrawn at a reset */
+} parc_phys_ranges_t;
+
+/* One launch per control step, capturable: for the envs whose reset_mask[e] != 0 (NULL = none) redraw the fields of field_mask, end a
+ * running push and draw the interval to the next one; for every other env, if push_tick, count push_next_in down and, at 0, draw a
+ * push (direction, magnitude, duration) and the next interval.  PARC_EINVAL for a NULL pointer, lo > hi, a non-finite bound, a
+ * non-positive lower bound of a log-uniform field, or a push duration / interval below 1 when pushes are on.  Random numbers: Philox4x32-10 keyed by
+ * `seed`, counter = (env, stream id, rng_state[0] lo, hi); rng_state[0] is the launch counter, advanced by the launch's last
+ * workgroup, rng_state[1] its ticket (as parc_rng_step).  ranges is passed by value (host memory). */
+int parc_phys_rand(void *stream, int n_envs, const int32_t *reset_mask, const parc_phys_ranges_t *ranges, uint64_t seed,
+                   uint64_t *rng_state, parc_sim_env_params_t *env_params);
+
 /* Recompute rigid_body_state (poses, velocities) from root_state / dof_state for the listed envs and zero
  * their contact forces: what the reference gets from refresh_rigid_body_state_tensor after a reset
  * (envs/ig_env.py:850-860).  env_ids int64 device pointer, NULL = all. */

@@ -45,7 +45,9 @@ struct Lane {
     unsigned children;        // bit c: body c is a child
 };
 
-__device__ __forceinline__ Lane load_lane(const parc_sim_model_t &m, int b) {
+// PHYS: mass and inertia scaled by the env's mass_scale (the only per-env value kept in lane registers: it replaces what they held)
+template <bool PHYS = false>
+__device__ __forceinline__ Lane load_lane(const parc_sim_model_t &m, int b, const parc_sim_env_params_t *ep = nullptr) {
     Lane L;
     const bool valid = b < m.num_bodies;
     const int bb = valid ? b : 0;
@@ -57,9 +59,12 @@ __device__ __forceinline__ Lane load_lane(const parc_sim_model_t &m, int b) {
     L.com = ld(m.com[bb]);
     L.lrot = Q4{m.local_rotation[bb][0], m.local_rotation[bb][1], m.local_rotation[bb][2], m.local_rotation[bb][3]};
     L.El = qmat(L.lrot);
-    L.mass = m.mass[bb];
+    L.mass = PARC_EP_MASS(bb);
 #pragma unroll
-    for (int i = 0; i < 6; ++i) L.io[i] = m.inertia_o[bb][i];
+    for (int i = 0; i < 6; ++i) {
+        if constexpr (PHYS) L.io[i] = m.inertia_o[bb][i] * ep->mass_scale;
+        else L.io[i] = m.inertia_o[bb][i];
+    }
     int d = 0;
     for (int a = bb; a > 0 && d < PARC_SIM_MAX_BODIES; a = m.parent[a]) ++d;
     L.depth = valid ? d : -1;
@@ -125,7 +130,9 @@ __device__ __forceinline__ ColumnSample sample_sphere(const parc_sim_model_t &m,
     return sample_columns(ter, k.P + mul(k.R, ld(m.sph_pos[s])) + env_off);
 }
 
-__device__ __forceinline__ ContactEval eval_contact(const parc_sim_model_t &m, const parc_terrain_t &ter, const ColumnSample &cs, const Kin &k, int s, float h) {
+template <bool PHYS = false>
+__device__ __forceinline__ ContactEval eval_contact(const parc_sim_model_t &m, const parc_terrain_t &ter, const ColumnSample &cs, const Kin &k, int s, float h,
+                                                    const parc_sim_env_params_t *ep = nullptr) {
     ContactEval ce;
     ce.hit = false;
     V3 rb = ld(m.sph_pos[s]);
@@ -138,19 +145,19 @@ __device__ __forceinline__ ContactEval eval_contact(const parc_sim_model_t &m, c
     V3 vpb = k.v.l + cross(k.v.a, ce.rc);
     float vn = dot(vpb, ce.nb);
     float d_eff = depth < m.contact_max_pen ? depth : m.contact_max_pen;
-    ce.cn = m.contact_cn;         // damper on approach AND on rebound (restitution 0); fn0 <= 0 below = no adhesion
-    float fn0 = m.contact_kn * d_eff - ce.cn * vn;
+    ce.cn = PARC_EP(contact_cn);         // damper on approach AND on rebound (restitution 0); fn0 <= 0 below = no adhesion
+    float fn0 = PARC_EP(contact_kn) * d_eff - ce.cn * vn;
     if (fn0 <= 0.f) return ce;
     V3 vt = vpb - vn * ce.nb;
     float vtn = p_sqrt(dot(vt, vt));
-    ce.ct = m.contact_ct;
-    float ct_cone = m.friction_mu * fn0 * p_rcp(vtn > 1e-4f ? vtn : 1e-4f);
+    ce.ct = PARC_EP(contact_ct);
+    float ct_cone = PARC_EP(friction_mu) * fn0 * p_rcp(vtn > 1e-4f ? vtn : 1e-4f);
     if (ct_cone < ce.ct) ce.ct = ct_cone;
     ce.F0 = fn0 * ce.nb - ce.ct * vt;
     // the known part of the contact point's world-velocity change, h w x v_centre (the body frame turns during the step): parc_sim_core.h pass1
     V3 wv = h * cross(k.v.a, k.v.l + cross(k.v.a, rb));
     float wvn = dot(wv, ce.nb);
-    ce.F0 = ce.F0 - ((ce.cn + h * m.contact_kn) * wvn) * ce.nb - ce.ct * (wv - wvn * ce.nb);
+    ce.F0 = ce.F0 - ((ce.cn + h * PARC_EP(contact_kn)) * wvn) * ce.nb - ce.ct * (wv - wvn * ce.nb);
     ce.hit = true;
     return ce;
 }
@@ -159,10 +166,12 @@ __device__ __forceinline__ ContactEval eval_contact(const parc_sim_model_t &m, c
 #define BPL_CC_FLOATS 11    // rc, nb, F0, cn, ct
 
 // MODE: PARC_SIM_CTL_*; th[3]: this joint's drive values in the modes other than pd (ctl_drive in parc_sim_core.h), unused by pd
-template <int MODE = PARC_SIM_CTL_PD>
+// PHYS: `ep` is this env's row of per-env physics parameters (in LDS in the kernel), each value read where it is used
+template <int MODE = PARC_SIM_CTL_PD, bool PHYS = false>
 __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, const Lane &L, int b, int maxd,
                                         LState &x, float h, float cweight, float *lds /* [16][BPL_CONTRIB] of this env */,
-                                        float *cc /* [BPL_CC_SLOTS][BPL_CC_FLOATS] of this lane */, const float *th = nullptr) {
+                                        float *cc /* [BPL_CC_SLOTS][BPL_CC_FLOATS] of this lane */, const float *th = nullptr,
+                                        const parc_sim_env_params_t *ep = nullptr) {
     Kin k;
     kin_pass(L, b, maxd, x, k);
     const bool valid = L.depth >= 0;
@@ -179,9 +188,11 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
         SV Iv = mul(IA, k.v);
         pA.a = cross(k.v.a, Iv.a) + cross(k.v.l, Iv.l);
         pA.l = cross(k.v.a, Iv.l);
-        V3 fg = mulT(k.R, v3(0.f, 0.f, -m.gravity * L.mass));
+        V3 fg = mulT(k.R, v3(0.f, 0.f, -PARC_EP(gravity) * L.mass));
         pA.a = pA.a - cross(L.com, fg);
         pA.l = pA.l - fg;
+        if constexpr (PHYS)
+            if (b == 0) ep_push(ep, k.R, L.com, pA);
         // per-link angular damping: the couple -c I_com w, with I_com w = I_o w + m c x (c x w)
         pA.a = pA.a + m.angular_damping * (mul(IA.A, k.v.a) + L.mass * cross(L.com, cross(L.com, k.v.a)));
     }
@@ -212,7 +223,7 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
             other.a = v3(q[0], q[1], q[2]); other.b = v3(q[3], q[4], q[5]); other.r = q[6];
             other.o = v3(q[7], q[8], q[9]); other.v = v3(q[10], q[11], q[12]); other.w = v3(q[13], q[14], q[15]);
             LinkHit hit;
-            if (!link_contact(m, mine, k.R, L.mass, other, q[16], h, b < ob, hit)) continue;
+            if (!link_contact<PHYS>(m, mine, k.R, L.mass, other, q[16], h, b < ob, hit, ep)) continue;
             pA.a = pA.a - hit.tau;
             pA.l = pA.l - hit.F;
             flink = flink + hit.F;
@@ -230,7 +241,7 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
         const ColumnSample cs = cs_next;
         const unsigned long long rest = mm & (mm - 1);
         if (rest) cs_next = sample_sphere(m, ter, env_off, k, __ffsll((long long)rest) - 1);
-        ContactEval ce = eval_contact(m, ter, cs, k, s, h);
+        ContactEval ce = eval_contact<PHYS>(m, ter, cs, k, s, h, ep);
         if (!ce.hit) continue;
         if (n_hit < BPL_CC_SLOTS) {
             float *o = cc + n_hit * BPL_CC_FLOATS;
@@ -240,7 +251,7 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
         } else {
             overflow |= 1ull << s;
         }
-        M3 Z = add(ident(ce.ct), outer(((ce.cn + h * m.contact_kn) - ce.ct) * ce.nb, ce.nb));
+        M3 Z = add(ident(ce.ct), outer(((ce.cn + h * PARC_EP(contact_kn)) - ce.ct) * ce.nb, ce.nb));
         M3 Sr = skew(ce.rc);
         M3 SZ = mul(Sr, Z);
         M3 SZS = mul(SZ, Sr);
@@ -264,9 +275,9 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
         if (L.jt == PARC_JOINT_SPHERICAL) {
             const V3 e = q_to_exp(x.jq);
             const float wv[3] = {x.jw.x, x.jw.y, x.jw.z}, ee[3] = {e.x, e.y, e.z};
-            ctl_drive<MODE>(m, L.d0, 3, ee, wv, th, h, tau, aug);
+            ctl_drive<MODE, PHYS>(m, L.d0, 3, ee, wv, th, h, tau, aug, ep);
         } else if (L.jt == PARC_JOINT_HINGE) {
-            ctl_drive<MODE>(m, L.d0, 1, &x.jang, &x.jw.x, th, h, tau, aug);
+            ctl_drive<MODE, PHYS>(m, L.d0, 1, &x.jang, &x.jw.x, th, h, tau, aug, ep);
         }
     } else if (L.jt == PARC_JOINT_SPHERICAL) {
         V3 err = q_to_exp(qmul(qconj(x.jq), x.tq)) - h * x.jw;
@@ -274,7 +285,7 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
         const float ev[3] = {err.x, err.y, err.z}, wv[3] = {x.jw.x, x.jw.y, x.jw.z}, ee[3] = {e.x, e.y, e.z};
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            float kp = m.kp[L.d0 + q], kd = m.kd[L.d0 + q];
+            float kp = PARC_EP_KP(L.d0 + q), kd = PARC_EP_KD(L.d0 + q);
             float t = kp * ev[q] - kd * wv[q];
             float lim = m.effort[L.d0 + q];
             float sc = (lim > 0.f && fabsf(t) > lim) ? lim * p_rcp(fabsf(t)) : 1.0f;
@@ -289,7 +300,7 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
         }
     } else if (L.jt == PARC_JOINT_HINGE) {
         float w = x.jw.x;
-        float kp = m.kp[L.d0], kd = m.kd[L.d0];
+        float kp = PARC_EP_KP(L.d0), kd = PARC_EP_KD(L.d0);
         float t = kp * (x.tang - x.jang - h * w) - kd * w;
         float lim = m.effort[L.d0];
         float sc = (lim > 0.f && fabsf(t) > lim) ? lim * p_rcp(fabsf(t)) : 1.0f;
@@ -412,17 +423,17 @@ __device__ __forceinline__ void substep(const parc_sim_model_t &m, const parc_te
             const V3 rc = v3(o[0], o[1], o[2]), nb = v3(o[3], o[4], o[5]), F0 = v3(o[6], o[7], o[8]);
             V3 dv = h * (a.l + cross(a.a, rc));
             float dvn = dot(dv, nb);
-            V3 F = F0 - (o[9] + h * m.contact_kn) * dvn * nb - o[10] * (dv - dvn * nb);
+            V3 F = F0 - (o[9] + h * PARC_EP(contact_kn)) * dvn * nb - o[10] * (dv - dvn * nb);
             float fnn = dot(F, nb);
             if (fnn < 0.f) F = F - fnn * nb;
             Fb = Fb + F;
         }
         for (unsigned long long mm = overflow; mm; mm &= mm - 1) {      // more simultaneous contacts than slots: re-evaluate
             const int so = __ffsll((long long)mm) - 1;
-            ContactEval ce = eval_contact(m, ter, sample_sphere(m, ter, env_off, k, so), k, so, h);
+            ContactEval ce = eval_contact<PHYS>(m, ter, sample_sphere(m, ter, env_off, k, so), k, so, h, ep);
             V3 dv = h * (a.l + cross(a.a, ce.rc));
             float dvn = dot(dv, ce.nb);
-            V3 F = ce.F0 - (ce.cn + h * m.contact_kn) * dvn * ce.nb - ce.ct * (dv - dvn * ce.nb);
+            V3 F = ce.F0 - (ce.cn + h * PARC_EP(contact_kn)) * dvn * ce.nb - ce.ct * (dv - dvn * ce.nb);
             float fnn = dot(F, ce.nb);
             if (fnn < 0.f) F = F - fnn * ce.nb;
             Fb = Fb + F;
@@ -526,12 +537,14 @@ __device__ __forceinline__ void store_lane_state(const Lane &L, int b, int maxd,
 // emulation runs, lane by lane in lock step).  `lds`: BPL_G * BPL_CONTRIB floats shared by the group, `cc`: this lane's contact cache.
 // MODE: PARC_SIM_CTL_*; the modes other than pd run in holds of `hold` substeps and write the torque of the last hold to
 // dof_torque [D] (torque / pd_exp / pd_1d, optional): parc_sim_core.h env_step_ctl.  The joint's drive values stay in lane registers.
-template <int MODE = PARC_SIM_CTL_PD>
+// PHYS: `ep` = this env's row of per-env physics parameters (a copy that all lanes of the env can read: LDS in the kernel); the caller
+// writes the push counter back.
+template <int MODE = PARC_SIM_CTL_PD, bool PHYS = false>
 __device__ __forceinline__ void step_lane(const parc_sim_model_t &m, const parc_terrain_t &ter, int b, float *root_state, float *dof_state,
                                           float *rigid_body_state, float *contact_forces, const float *env_offset, const float *action,
                                           const float *act_lo, const float *act_hi, int n_sub, float h, float *lds, float *cc, int hold = 1,
-                                          float *dof_torque = nullptr) {
-    const Lane L = load_lane(m, b);
+                                          float *dof_torque = nullptr, const parc_sim_env_params_t *ep = nullptr) {
+    const Lane L = load_lane<PHYS>(m, b, ep);
     int maxd = L.depth;
 #pragma unroll
     for (int o = 8; o >= 1; o >>= 1) {
@@ -543,7 +556,7 @@ __device__ __forceinline__ void step_lane(const parc_sim_model_t &m, const parc_
     const V3 off = ld(env_offset);
     const float w = 1.0f / (float)n_sub;
     if constexpr (MODE == PARC_SIM_CTL_PD) {
-        for (int s = 0; s < n_sub; ++s) substep(m, ter, off, L, b, maxd, x, h, w, lds, cc);
+        for (int s = 0; s < n_sub; ++s) substep<MODE, PHYS>(m, ter, off, L, b, maxd, x, h, w, lds, cc, nullptr, ep);
         store_lane_state(L, b, maxd, x, root_state, dof_state, rigid_body_state, contact_forces);
     } else {
         const int dd = L.jt == PARC_JOINT_SPHERICAL ? 3 : (L.jt == PARC_JOINT_HINGE ? 1 : 0);
@@ -556,11 +569,11 @@ __device__ __forceinline__ void step_lane(const parc_sim_model_t &m, const parc_
         int left = 0;      // substeps left in the current hold
         for (int s = 0; s < n_sub; ++s) {
             if (ctl_explicit_pd<MODE>() && left == 0) {
-                ctl_hold_torque<MODE>(m, L.jt, L.d0, L.ax, x.jq, x.jang, x.jw, x.tq, x.tang, th);
+                ctl_hold_torque<MODE, PHYS>(m, L.jt, L.d0, L.ax, x.jq, x.jang, x.jw, x.tq, x.tang, th, ep);
                 left = hold;
             }
             --left;
-            substep<MODE>(m, ter, off, L, b, maxd, x, h, w, lds, cc, th);
+            substep<MODE, PHYS>(m, ter, off, L, b, maxd, x, h, w, lds, cc, th, ep);
         }
         store_lane_state(L, b, maxd, x, root_state, dof_state, rigid_body_state, contact_forces);
         if (dof_torque && MODE != PARC_SIM_CTL_VEL) {

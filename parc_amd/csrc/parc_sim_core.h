@@ -351,6 +351,24 @@ PARC_HD bool sphere_vs_columns(const parc_terrain_t &t, V3 p, float rho, float &
     return columns_contact(t, sample_columns(t, p), rho, depth, n);
 }
 
+// ---- per-env physics parameters (parc_sim_env_params_t, parc_sim_step_phys).  PHYS is a compile-time switch of every function that reads
+// one of the randomisable constants: false = the model struct's value (ep unused, the code of the kernels without a table), true = the
+// env's row `ep`.  The scales multiply the model's value where it is read.
+// (Macros, so that with PHYS = false the compiler sees the very expression `m.field` the kernels without a table were written with.)
+#define PARC_EP(field) (PHYS ? ep->field : m.field)
+#define PARC_EP_KP(d) (PHYS ? m.kp[d] * ep->kp_scale : m.kp[d])
+#define PARC_EP_KD(d) (PHYS ? m.kd[d] * ep->kd_scale : m.kd[d])
+#define PARC_EP_MASS(b) (PHYS ? m.mass[b] * ep->mass_scale : m.mass[b])
+// the push of the env's row as an external force on the root link, body coordinates (R: the root's rotation): a force F at the centre of
+// mass `com` subtracts [com x F; F] from the root's bias force, like gravity
+PARC_HD void ep_push(const parc_sim_env_params_t *ep, const M3 &R, V3 com, SV &p) {
+    if (ep->push_steps_left > 0) {
+        const V3 f = mulT(R, ld(ep->push_force));
+        p.a = p.a - cross(com, f);
+        p.l = p.l - f;
+    }
+}
+
 PARC_HD float clampf01(float v) { return v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
 
 // ---- link-link contact (self-collision) -----------------------------------------------------------------------------------
@@ -418,8 +436,9 @@ struct LinkHit {
 // regularised Coulomb, |Ft| = min(ct |vt|, mu fn) against the tangential relative velocity, applied to both bodies at the COMMON point
 // midway between the two surface points (equal and opposite forces on one line of action: no net force, no net torque); the normal
 // forces act at the two surface points, which lie on one line along n.
+template <bool PHYS = false>
 PARC_HD bool link_contact(const parc_sim_model_t &m, const CapsuleW &A, const M3 &R, float mass_a, const CapsuleW &B, float mass_b, float h,
-                          bool a_first, LinkHit &hit) {
+                          bool a_first, LinkHit &hit, const parc_sim_env_params_t *ep = nullptr) {
     {
         const V3 cc = A.c - B.c;
         const float far = A.ext + B.ext;
@@ -446,8 +465,8 @@ PARC_HD bool link_contact(const parc_sim_model_t &m, const CapsuleW &A, const M3
     const float mu = mass_a * mass_b * p_rcp(mass_a + mass_b);
     const float ih = p_rcp(h);
     const float kcap = mu * ih * ih, ccap = 0.5f * mu * ih;
-    const float kn = m.contact_kn < kcap ? m.contact_kn : kcap;
-    const float cn = vn < 0.f ? (m.contact_cn < ccap ? m.contact_cn : ccap) : 0.f;
+    const float kn = PARC_EP(contact_kn) < kcap ? PARC_EP(contact_kn) : kcap;
+    const float cn = vn < 0.f ? (PARC_EP(contact_cn) < ccap ? PARC_EP(contact_cn) : ccap) : 0.f;
     const float d_eff = pen < m.contact_max_pen ? pen : m.contact_max_pen;
     const float fn = kn * d_eff - cn * vn;
     if (fn <= 0.f) return false;
@@ -460,8 +479,8 @@ PARC_HD bool link_contact(const parc_sim_model_t &m, const CapsuleW &A, const M3
     if (vt2 > 1e-12f) {
         const float vtl = p_sqrt(vt2);
         const float ctc = 0.5f * ccap;
-        const float ct = m.contact_ct < ctc ? m.contact_ct : ctc;
-        const float lim = m.friction_mu * fn;
+        const float ct = PARC_EP(contact_ct) < ctc ? PARC_EP(contact_ct) : ctc;
+        const float lim = PARC_EP(friction_mu) * fn;
         const float ft = ct * vtl < lim ? ct * vtl : lim;
         Ft = (-ft * p_rcp(vtl)) * vt;
     }
@@ -491,7 +510,9 @@ PARC_HD CapsuleW capsule_world(const parc_sim_model_t &m, int b, const M3 &R, V3
 // Forward kinematics + velocities + bias terms (ABA pass 1) and per-body contact impedance.
 // After this call s.IA / s.pA hold the rigid-body inertia + contact augmentation and the bias force minus
 // external forces; contact bookkeeping needed to report forces afterwards is recomputed in report_contacts().
-PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, const State &x, Scratch &s, float h) {
+template <bool PHYS = false>
+PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, const State &x, Scratch &s, float h,
+                   const parc_sim_env_params_t *ep = nullptr) {
     const int B = m.num_bodies;
     s.R[0] = qmat(x.root_rot);
     s.P[0] = x.root_pos;
@@ -517,10 +538,17 @@ PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_
     }
     PARC_LOOP(1)
     for (int i = 0; i < B; ++i) {
-        const float mass = m.mass[i];
+        const float mass = PARC_EP_MASS(i);
         V3 hc = mass * ld(m.com[i]);
         SI I;
+        float io_s[6];
         const float *io = m.inertia_o[i];
+        if constexpr (PHYS) {       // mass_scale scales the inertia with the mass
+            for (int q = 0; q < 6; ++q) io_s[q] = m.inertia_o[i][q] * ep->mass_scale;
+            io = io_s;
+        } else {
+            (void)io_s;
+        }
         I.A.m[0] = io[0]; I.A.m[1] = io[1]; I.A.m[2] = io[2];
         I.A.m[3] = io[1]; I.A.m[4] = io[3]; I.A.m[5] = io[4];
         I.A.m[6] = io[2]; I.A.m[7] = io[4]; I.A.m[8] = io[5];
@@ -532,9 +560,11 @@ PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_
         SV p;
         p.a = cross(v.a, Iv.a) + cross(v.l, Iv.l);
         p.l = cross(v.a, Iv.l);
-        V3 fg = mulT(s.R[i], v3(0.f, 0.f, -m.gravity * mass));   // gravity at the centre of mass
+        V3 fg = mulT(s.R[i], v3(0.f, 0.f, -PARC_EP(gravity) * mass));   // gravity at the centre of mass
         p.a = p.a - cross(ld(m.com[i]), fg);
         p.l = p.l - fg;
+        if constexpr (PHYS)
+            if (i == 0) ep_push(ep, s.R[0], ld(m.com[0]), p);
         // per-link angular damping: the couple -c I_com w, with I_com w = I_o w + m c x (c x w)
         V3 cm = ld(m.com[i]);
         p.a = p.a + m.angular_damping * (mul(I.A, v.a) + mass * cross(cm, cross(cm, v.a)));
@@ -549,7 +579,8 @@ PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_
         for (int j = 0; j < B; ++j) {
             if (!((m.self_mask[i] >> j) & 1u) || !(m.cap_radius[j] > 0.f)) continue;
             LinkHit hit;
-            if (!link_contact(m, ci, s.R[i], m.mass[i], capsule_world(m, j, s.R[j], s.P[j], s.v[j]), m.mass[j], h, i < j, hit)) continue;
+            if (!link_contact<PHYS>(m, ci, s.R[i], PARC_EP_MASS(i), capsule_world(m, j, s.R[j], s.P[j], s.v[j]), PARC_EP_MASS(j), h, i < j, hit, ep))
+                continue;
             s.pA[i].a = s.pA[i].a - hit.tau;
             s.pA[i].l = s.pA[i].l - hit.F;
             s.flink[i] = s.flink[i] + hit.F;
@@ -569,13 +600,13 @@ PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_
         V3 nb = mulT(s.R[b], n);
         float vn = dot(vpb, nb);
         float d_eff = depth < m.contact_max_pen ? depth : m.contact_max_pen;
-        float cn = m.contact_cn;      // damper on approach AND on rebound (restitution 0, envs/ig_env.py:517,733); fn0 <= 0 below = no adhesion
-        float fn0 = m.contact_kn * d_eff - cn * vn;
+        float cn = PARC_EP(contact_cn);      // damper on approach AND on rebound (restitution 0, envs/ig_env.py:517,733); fn0 <= 0 below = no adhesion
+        float fn0 = PARC_EP(contact_kn) * d_eff - cn * vn;
         if (fn0 <= 0.f) continue;
         V3 vt = vpb - vn * nb;
         float vtn = p_sqrt(dot(vt, vt));
-        float ct = m.contact_ct;
-        float ct_cone = m.friction_mu * fn0 * p_rcp(vtn > 1e-4f ? vtn : 1e-4f);
+        float ct = PARC_EP(contact_ct);
+        float ct_cone = PARC_EP(friction_mu) * fn0 * p_rcp(vtn > 1e-4f ? vtn : 1e-4f);
         if (ct_cone < ct) ct = ct_cone;
         V3 F0 = fn0 * nb - ct * vt;
         // The impedance Z acts on the change of the contact point's WORLD velocity over the step.  The contact point of a sample sphere is
@@ -586,10 +617,10 @@ PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_
         {
             V3 wv = h * cross(s.v[b].a, s.v[b].l + cross(s.v[b].a, rb));
             float wvn = dot(wv, nb);
-            F0 = F0 - ((cn + h * m.contact_kn) * wvn) * nb - ct * (wv - wvn * nb);
+            F0 = F0 - ((cn + h * PARC_EP(contact_kn)) * wvn) * nb - ct * (wv - wvn * nb);
         }
         // Z = (cn + h kn) n n^T + ct (1 - n n^T), body coordinates
-        M3 Z = add(ident(ct), outer(((cn + h * m.contact_kn) - ct) * nb, nb));
+        M3 Z = add(ident(ct), outer(((cn + h * PARC_EP(contact_kn)) - ct) * nb, nb));
         M3 Sr = skew(rc);
         M3 SZ = mul(Sr, Z);
         // A += h * (-Sr Z Sr), B += h * (Sr Z), C += h * Z
@@ -606,7 +637,9 @@ PARC_HD void pass1(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_
 }
 
 // After the accelerations are known: realised contact force of every body, world frame (F+ = F0 - Z h J a)
-PARC_HD void report_contacts(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, const Scratch &s, float h, float weight, State &x) {
+template <bool PHYS = false>
+PARC_HD void report_contacts(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, const Scratch &s, float h, float weight, State &x,
+                             const parc_sim_env_params_t *ep = nullptr) {
     PARC_LOOP(3)
     for (int k = 0; k < m.num_spheres; ++k) {
         const int b = m.sph_body[k];
@@ -620,18 +653,18 @@ PARC_HD void report_contacts(const parc_sim_model_t &m, const parc_terrain_t &te
         V3 nb = mulT(s.R[b], n);
         float vn = dot(vpb, nb);
         float d_eff = depth < m.contact_max_pen ? depth : m.contact_max_pen;
-        float cn = m.contact_cn;      // damper on approach AND on rebound (restitution 0, envs/ig_env.py:517,733); fn0 <= 0 below = no adhesion
-        float fn0 = m.contact_kn * d_eff - cn * vn;
+        float cn = PARC_EP(contact_cn);      // damper on approach AND on rebound (restitution 0, envs/ig_env.py:517,733); fn0 <= 0 below = no adhesion
+        float fn0 = PARC_EP(contact_kn) * d_eff - cn * vn;
         if (fn0 <= 0.f) continue;
         V3 vt = vpb - vn * nb;
         float vtn = p_sqrt(dot(vt, vt));
-        float ct = m.contact_ct;
-        float ct_cone = m.friction_mu * fn0 * p_rcp(vtn > 1e-4f ? vtn : 1e-4f);
+        float ct = PARC_EP(contact_ct);
+        float ct_cone = PARC_EP(friction_mu) * fn0 * p_rcp(vtn > 1e-4f ? vtn : 1e-4f);
         if (ct_cone < ct) ct = ct_cone;
         V3 F0 = fn0 * nb - ct * vt;
         V3 dv = h * (s.a[b].l + cross(s.a[b].a, rc) + cross(s.v[b].a, s.v[b].l + cross(s.v[b].a, rb)));   // world-velocity change of the contact point (pass1)
         float dvn = dot(dv, nb);
-        V3 F = F0 - (cn + h * m.contact_kn) * dvn * nb - ct * (dv - dvn * nb);
+        V3 F = F0 - (cn + h * PARC_EP(contact_kn)) * dvn * nb - ct * (dv - dvn * nb);
         float fnn = dot(F, nb);
         if (fnn < 0.f) F = F - fnn * nb;   // no adhesion in what is reported
         x.cforce[b] = x.cforce[b] + weight * mul(s.R[b], F);
@@ -653,20 +686,21 @@ PARC_HD constexpr bool ctl_explicit_pd() { return MODE == PARC_SIM_CTL_PD_EXP ||
 // anim/kin_char_model.py:552-581), projected on the axis for a hinge, so it wraps to (-pi, pi]; pd_1d: diff = tar - q, no wrap (a spherical
 // joint, which the env refuses, takes the difference of the exp-maps).  Unlike the pd drive, where effort <= 0 means "unlimited", this is
 // the reference's torch.clip: effort 0 gives torque 0.
-template <int MODE>
-PARC_HD void ctl_hold_torque(const parc_sim_model_t &m, int jt, int d0, V3 ax, Q4 jq, float jang, V3 jw, Q4 tq, float tang, float *th) {
+template <int MODE, bool PHYS = false>
+PARC_HD void ctl_hold_torque(const parc_sim_model_t &m, int jt, int d0, V3 ax, Q4 jq, float jang, V3 jw, Q4 tq, float tang, float *th,
+                             const parc_sim_env_params_t *ep = nullptr) {
     if (jt == PARC_JOINT_SPHERICAL) {
         const V3 diff = MODE == PARC_SIM_CTL_PD_EXP ? q_to_exp(qnormalize(qmul(qconj(jq), tq))) : q_to_exp(tq) - q_to_exp(jq);
         const float dv[3] = {diff.x, diff.y, diff.z}, wv[3] = {jw.x, jw.y, jw.z};
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float lim = m.effort[d0 + k];
-            th[k] = clampf(m.kp[d0 + k] * dv[k] - m.kd[d0 + k] * wv[k], -lim, lim);
+            th[k] = clampf(PARC_EP_KP(d0 + k) * dv[k] - PARC_EP_KD(d0 + k) * wv[k], -lim, lim);
         }
     } else if (jt == PARC_JOINT_HINGE) {
         const float diff = MODE == PARC_SIM_CTL_PD_EXP ? dot(ax, q_to_exp(qnormalize(qmul(qconj(jq), exp_to_q(tang * ax))))) : tang - jang;
         const float lim = m.effort[d0];
-        th[0] = clampf(m.kp[d0] * diff - m.kd[d0] * jw.x, -lim, lim);
+        th[0] = clampf(PARC_EP_KP(d0) * diff - PARC_EP_KD(d0) * jw.x, -lim, lim);
     }
 }
 
@@ -674,13 +708,13 @@ PARC_HD void ctl_hold_torque(const parc_sim_model_t &m, int jt, int d0, V3 ax, Q
 //   vel:    implicit velocity drive, tau = kd (v_tar - qdot), D += armature + h kd, scaled down like the pd drive when |tau| > effort > 0
 //   torque, pd_exp, pd_1d: explicit, tau = th, D += armature
 // plus the joint-limit springs of the pd path.
-template <int MODE>
+template <int MODE, bool PHYS = false>
 PARC_HD void ctl_drive(const parc_sim_model_t &m, int d0, int dd, const float *ee, const float *wv, const float *th, float h, float *tau,
-                       float *aug) {
+                       float *aug, const parc_sim_env_params_t *ep = nullptr) {
 #pragma unroll
     for (int k = 0; k < dd; ++k) {
         if (MODE == PARC_SIM_CTL_VEL) {
-            const float kd = m.kd[d0 + k];
+            const float kd = PARC_EP_KD(d0 + k);
             const float t = kd * (th[k] - wv[k]);
             const float lim = m.effort[d0 + k];
             const float sc = (lim > 0.f && fabsf(t) > lim) ? lim * p_rcp(fabsf(t)) : 1.0f;
@@ -701,11 +735,11 @@ PARC_HD void ctl_drive(const parc_sim_model_t &m, int d0, int dd, const float *e
 
 // ABA passes 2 and 3 + integration: one substep of length h.  MODE: PARC_SIM_CTL_*; th [D]: the per-dof drive values of the modes other
 // than pd (ctl_drive), unused by pd.
-template <int MODE = PARC_SIM_CTL_PD>
+template <int MODE = PARC_SIM_CTL_PD, bool PHYS = false>
 PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 env_off, State &x, Scratch &s, float h, float cweight,
-                     const float *th = nullptr) {
+                     const float *th = nullptr, const parc_sim_env_params_t *ep = nullptr) {
     const int B = m.num_bodies;
-    pass1(m, ter, env_off, x, s, h);
+    pass1<PHYS>(m, ter, env_off, x, s, h, ep);
     // ---- joint drives (implicit PD) and limits: tau and the diagonal augmentation of D
     // ---- pass 2: leaves -> root
     PARC_LOOP(4)
@@ -720,7 +754,7 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
             if constexpr (MODE != PARC_SIM_CTL_PD) {
                 const V3 e = q_to_exp(x.jq[i]);
                 const float wv[3] = {x.jw[i].x, x.jw[i].y, x.jw[i].z}, ee[3] = {e.x, e.y, e.z};
-                ctl_drive<MODE>(m, d0, 3, ee, wv, th + d0, h, tau, aug);
+                ctl_drive<MODE, PHYS>(m, d0, 3, ee, wv, th + d0, h, tau, aug, ep);
             } else {
             // predicted rotation error in the child frame: log(q^-1 q_target) - h w
             V3 err = q_to_exp(qmul(qconj(x.jq[i]), x.tq[i])) - h * x.jw[i];
@@ -728,7 +762,7 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
             const float ev[3] = {err.x, err.y, err.z}, wv[3] = {x.jw[i].x, x.jw[i].y, x.jw[i].z}, ee[3] = {e.x, e.y, e.z};
             PARC_LOOP(5)
             for (int k = 0; k < 3; ++k) {
-                float kp = m.kp[d0 + k], kd = m.kd[d0 + k];
+                float kp = PARC_EP_KP(d0 + k), kd = PARC_EP_KD(d0 + k);
                 float t = kp * ev[k] - kd * wv[k];
                 float lim = m.effort[d0 + k];
                 float sc = (lim > 0.f && fabsf(t) > lim) ? lim * p_rcp(fabsf(t)) : 1.0f;
@@ -763,9 +797,9 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
             float tau, aug;
             if constexpr (MODE != PARC_SIM_CTL_PD) {
                 const float ang = x.jang[i];
-                ctl_drive<MODE>(m, d0, 1, &ang, &w, th + d0, h, &tau, &aug);
+                ctl_drive<MODE, PHYS>(m, d0, 1, &ang, &w, th + d0, h, &tau, &aug, ep);
             } else {
-            float kp = m.kp[d0], kd = m.kd[d0];
+            float kp = PARC_EP_KP(d0), kd = PARC_EP_KD(d0);
             float t = kp * (x.tang[i] - x.jang[i] - h * w) - kd * w;
             float lim = m.effort[d0];
             float sc = (lim > 0.f && fabsf(t) > lim) ? lim * p_rcp(fabsf(t)) : 1.0f;
@@ -850,7 +884,7 @@ PARC_HD void substep(const parc_sim_model_t &m, const parc_terrain_t &ter, V3 en
         }
         s.a[i] = a1;
     }
-    if (cweight > 0.f) report_contacts(m, ter, env_off, s, h, cweight, x);
+    if (cweight > 0.f) report_contacts<PHYS>(m, ter, env_off, s, h, cweight, x, ep);
     // ---- integrate (semi-implicit Euler): velocities first, then positions with the new velocities
     // The root's linear velocity advances in WORLD coordinates: v_w += h R (a_sp + w x v) (the classical acceleration of the origin).
     // Advancing its body coordinates by h a_sp instead turns them by (1 - h [w]), which stretches |v| by 1 + h^2 w^2 / 2 per substep (16 %
@@ -980,10 +1014,12 @@ PARC_HD void publish_bodies(const parc_sim_model_t &m, const State &x, float *ri
 // substeps (one gym.simulate each).  pd / vel / torque keep their targets for the whole step; pd_exp / pd_1d recompute their torque at the
 // start of every hold (IGCharEnv._apply_forces before each gym.simulate, ig_char_env.py:378-395).  dof_torque [D] (optional): the
 // torque of the last hold (torque / pd_exp / pd_1d), what the reference leaves in _char_action_buffer.
-template <int MODE>
+// PHYS: the env's row of per-env physics parameters `ep` replaces the model's constants (parc_sim_step_phys); the row's push counter goes down
+// by one per call.
+template <int MODE, bool PHYS = false>
 PARC_HD void env_step_ctl(const parc_sim_model_t &m, const parc_terrain_t &ter, const float *env_offset, float *root_state, float *dof_state,
                           float *rigid_body_state, float *contact_forces, const float *action, const float *act_lo, const float *act_hi,
-                          int n_sub, float h, Scratch &s, int hold, float *dof_torque) {
+                          int n_sub, float h, Scratch &s, int hold, float *dof_torque, parc_sim_env_params_t *ep = nullptr) {
     State x;
 #if defined(PARC_SIM_FILL_STATE)     // host test builds: start from a known byte pattern (oracle/Makefile `poison`)
     memset((void *)&x, PARC_SIM_FILL_STATE, sizeof x);
@@ -999,17 +1035,28 @@ PARC_HD void env_step_ctl(const parc_sim_model_t &m, const parc_terrain_t &ter, 
     for (int k = 0; k < n_sub; ++k) {
         if (ctl_explicit_pd<MODE>() && left == 0) {
             for (int i = 1; i < m.num_bodies; ++i)
-                ctl_hold_torque<MODE>(m, m.joint_type[i], m.dof_idx[i], ld(m.joint_axis[i]), x.jq[i], x.jang[i], x.jw[i], x.tq[i], x.tang[i],
-                                      th + m.dof_idx[i]);
+                ctl_hold_torque<MODE, PHYS>(m, m.joint_type[i], m.dof_idx[i], ld(m.joint_axis[i]), x.jq[i], x.jang[i], x.jw[i], x.tq[i], x.tang[i],
+                                            th + m.dof_idx[i], ep);
             left = hold;
         }
         --left;
-        substep<MODE>(m, ter, off, x, s, h, w, th);
+        substep<MODE, PHYS>(m, ter, off, x, s, h, w, th, ep);
     }
     store_state(m, x, s, root_state, dof_state, rigid_body_state, contact_forces);
     publish_bodies(m, x, rigid_body_state, contact_forces);
     if (dof_torque && MODE != PARC_SIM_CTL_PD && MODE != PARC_SIM_CTL_VEL)
         for (int d = 0; d < m.dof_size; ++d) dof_torque[d] = th[d];
+    if constexpr (PHYS)
+        if (ep->push_steps_left > 0) ep->push_steps_left -= 1;
+}
+
+// The rules a row of the table has to keep (parc_sim_step_phys returns PARC_EINVAL otherwise); x - x == 0 only for a finite x
+PARC_HD bool env_params_valid(const parc_sim_env_params_t &p) {
+    const bool pos = p.mass_scale > 0.f && p.contact_kn > 0.f && p.kp_scale > 0.f && p.mass_scale - p.mass_scale == 0.f &&
+                     p.contact_kn - p.contact_kn == 0.f && p.kp_scale - p.kp_scale == 0.f;
+    const bool nonneg = p.friction_mu >= 0.f && p.contact_cn >= 0.f && p.contact_ct >= 0.f && p.kd_scale >= 0.f && p.push_steps_left >= 0;
+    const float sum = p.gravity + p.friction_mu + p.contact_cn + p.contact_ct + p.kd_scale + p.push_force[0] + p.push_force[1] + p.push_force[2];
+    return pos && nonneg && sum - sum == 0.f;
 }
 
 // One env step with the PD targets held (the pd control mode)

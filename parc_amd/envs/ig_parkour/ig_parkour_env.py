@@ -85,7 +85,8 @@ class IGParkourEnv(base_env.BaseEnv):
         self._control_mode = env_config["control_mode"]
         check_control_mode(km, self._control_mode)
         self._ctl = _hip_sim.CONTROL_MODES[self._control_mode]
-        self._sim_model = SimModel(km)
+        # gravity (ig_env.py:139-142): `gravity_z` of the YAML, -9.81 when absent; the model struct holds its magnitude along -z
+        self._sim_model = SimModel(km, gravity=-float(env_config.get("gravity_z", -9.81)))
         low, high = action_bounds(km, self._sim_model, self._control_mode)
         self._action_space = Box(low=low.astype(np.float32), high=high.astype(np.float32))
         self._action_bound_low = torch.tensor(low, dtype=torch.float32, device=device)
@@ -119,6 +120,12 @@ class IGParkourEnv(base_env.BaseEnv):
 
         self._build_sim_tensors(env_config)
         self._build_data_buffers()
+        # per-env physics parameters (parc_sim_step_phys): off - no table, the launches of always - unless the YAML has a
+        # `physics_rand` block or a setter is called
+        self._phys_table = None
+        self._phys_ranges = None
+        if env_config.get("physics_rand") is not None:
+            self._enable_physics_params(env_config["physics_rand"])
         if n_mg > 0:
             self._mgdm_env.attach(self._core, n_dm)
             self._mgdm_env.replan()          # the first plans exist before the first observation (ig_parkour_env.py:796-798)
@@ -323,6 +330,9 @@ class IGParkourEnv(base_env.BaseEnv):
         def sig(v):
             return ("tensor", v.data_ptr()) if torch.is_tensor(v) else v        # device-resident values are read by the graph itself
         out = (float(self._cfg.struct.episode_length),)
+        if self._phys_table is not None:      # the table is a launch argument, and with it the step is another kernel
+            out += ("phys", self._phys_table.data_ptr(), self._phys_ranges is not None and bool(self._phys_ranges.field_mask),
+                    self._phys_ranges is not None and self._phys_ranges.push_interval[1] > 0)
         if dm is not None:
             out += (dm._rand_reset, dm._demo_mode, sig(dm._rand_root_pos_offset_scale), sig(dm._motion_start_time_fraction), dm.has_state_offsets())
         mg = self._mgdm_env
@@ -380,6 +390,10 @@ class IGParkourEnv(base_env.BaseEnv):
             self._reset_mgdm(env_ids[env_ids >= n_dm] - n_dm)
         else:
             self._reset_dm(env_ids)
+        if self._phys_ranges is not None and len(env_ids) > 0:
+            self._phys_mask.zero_()
+            self._phys_mask[env_ids] = 1
+            self._phys_rand(self._phys_mask)
         self._update_info()
         return self._obs_buf, self._info
 
@@ -468,6 +482,14 @@ class IGParkourEnv(base_env.BaseEnv):
             self._mgdm_env.host_step_replayed(self._timestep)
 
     def reset_done(self, done=None):
+        """reset(nonzero(done)) on the device (_reset_done_rows), then - with a `physics_rand` block - the physics parameters of the rows
+        that restarted are redrawn (parc_phys_rand under the restart chain's own mask: fixed-shape, capturable)"""
+        out = self._reset_done_rows(done)
+        if self._phys_ranges is not None:
+            self._phys_rand(self._core.reset_mask)
+        return out
+
+    def _reset_done_rows(self, done=None):
         """reset(nonzero(done)) without the nonzero: the same state changes as ``reset(env_ids)`` for every env whose
         done flag is set, as fixed-shape device work (no host sync, capturable in the rollout hipGraph).  Candidates are
         drawn for all envs and applied where the flag is set (parc_reset_apply), the reference pose / character state /
@@ -563,7 +585,10 @@ class IGParkourEnv(base_env.BaseEnv):
             return self._step_sub_envs(act)
         # _pre_physics_step + _physics_step: PD targets = clipped action, sim_steps x substeps at h; _update_time (ig_env.py:862-865:
         # timestep += 1, time = timestep * dt) rides in the same launch
-        if self._ctl != _hip_sim.CONTROL_MODES["pd"]:
+        if self._phys_table is not None:
+            self._phys_push_tick()
+            self._sim_rows(act, 0, self._num_envs, c._terrain_struct)
+        elif self._ctl != _hip_sim.CONTROL_MODES["pd"]:
             self._sim_rows(act, 0, self._num_envs, c._terrain_struct)
         else:
             L = _hip.lib()
@@ -591,6 +616,15 @@ class IGParkourEnv(base_env.BaseEnv):
         c = self._core
         B, D = self._cfg.num_bodies, self._cfg.dof_size
         p = _hip.ptr
+        if self._phys_table is not None:
+            # per-env physics parameters: every control mode, pd included, through the table's kernel
+            _hip.check(_hip.lib().parc_sim_step_phys(_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]),
+                                                     p(c.dof_state[e0 * D:]), p(c.rigid_body_state[e0 * B:]), p(c.contact_forces[e0 * B:]),
+                                                     p(c.env_offsets[e0:]), p(act[e0:]), p(self._action_bound_low), p(self._action_bound_high),
+                                                     self._sim_steps * self._substeps, self._sim_h, self._substeps, p(self._phys_table[e0:]),
+                                                     self._ctl, p(self._dof_torque[e0:]) if self._dof_torque is not None else None,
+                                                     p(self._timestep_buf[e0:]), p(self._time_buf[e0:]), float(self._timestep)), "parc_sim_step_phys")
+            return
         if self._ctl != _hip_sim.CONTROL_MODES["pd"]:
             # the other control modes: holds of `substeps` (one gym.simulate each); pd_exp / pd_1d ignore the bounds (unclipped targets)
             _hip.check(_hip.lib().parc_sim_step_ctl(_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]),
@@ -613,6 +647,8 @@ class IGParkourEnv(base_env.BaseEnv):
         c, mg = self._core, self._mgdm_env
         n_dm, n_mg = self._num_dm_envs, self._num_mgdm_envs
         mg.pre_physics_step()
+        if self._phys_table is not None:
+            self._phys_push_tick()
         if n_dm > 0:
             self._sim_rows(act, 0, n_dm, c._terrain_struct)
         self._sim_rows(act, n_dm, n_mg, mg.terrain_struct())
@@ -632,6 +668,120 @@ class IGParkourEnv(base_env.BaseEnv):
         if self._write_agent_states_flag:
             self.write_agent_states()
         return self._obs_buf, self._reward_buf, self._done_buf, self._info
+
+    # ------------------------------------------------------------------ per-env physics parameters and pushes (include/parc_sim.h)
+    def _enable_physics_params(self, rand_cfg=None):
+        """Allocate the per-env table (rows = the model's own constants, scales 1, no push: the step computes what it computed before, bit
+        for bit) and switch every simulator launch to parc_sim_step_phys.  rand_cfg: the YAML's `physics_rand` block - per field a pair
+        [lo, hi] (redrawn at every reset of an env; contact constants and mass_scale log-uniformly) or a scalar (fixed for all envs), and
+        `push: {interval_s, force, duration_s}`.  Everything a capture would otherwise allocate lazily - table, mask, generator cells -
+        exists from here on."""
+        N, dev = self._num_envs, self._device
+        st = self._sim_model.struct
+        row = _hip_sim.EnvParamsS(gravity=st.gravity, friction_mu=st.friction_mu, contact_kn=st.contact_kn, contact_cn=st.contact_cn,
+                                  contact_ct=st.contact_ct, mass_scale=1.0, kp_scale=1.0, kd_scale=1.0)
+        raw = torch.frombuffer(bytearray(bytes(row)), dtype=torch.float32)
+        self._phys_table = raw.to(dev).repeat(N, 1).contiguous()                  # [N, 16] words, float view
+        ti = self._phys_table.view(torch.int32)
+        col = _hip_sim.PHYS_COLUMN
+        views = {f: self._phys_table[:, col[f]] for f in _hip_sim.PHYS_FIELDS}
+        views["push_force"] = self._phys_table[:, col["push_force"]:col["push_force"] + 3]
+        views["push_steps_left"] = ti[:, col["push_steps_left"]]
+        views["push_next_in"] = ti[:, col["push_next_in"]]
+        self._phys_views = views
+        if not rand_cfg:
+            return
+        rg = _hip_sim.PhysRangesS()
+        unknown = set(rand_cfg) - set(_hip_sim.PHYS_FIELDS) - {"push"}
+        assert not unknown, "physics_rand: unknown keys {}".format(sorted(unknown))
+        for k, f in enumerate(_hip_sim.PHYS_FIELDS):
+            if f not in rand_cfg:
+                continue
+            v = rand_cfg[f]
+            if np.ndim(v) == 0:                     # a scalar: fixed at this value for all envs
+                self._check_phys_values(f, torch.tensor([float(v)]))
+                views[f].fill_(float(v))
+                continue
+            lo, hi = float(v[0]), float(v[1])
+            assert len(v) == 2 and lo <= hi, "physics_rand.{}: [lo, hi] expected".format(f)
+            self._check_phys_values(f, torch.tensor([lo, hi]))
+            getattr(rg, f)[0], getattr(rg, f)[1] = lo, hi
+            rg.field_mask |= 1 << k
+        push = rand_cfg.get("push")
+        if push is not None:
+            def pair(v):
+                return (float(v), float(v)) if np.ndim(v) == 0 else (float(v[0]), float(v[1]))
+            (i0, i1), (f0, f1), (d0, d1) = pair(push["interval_s"]), pair(push["force"]), pair(push["duration_s"])
+            assert 0 < i0 <= i1 and 0 <= f0 <= f1 and 0 < d0 <= d1, "physics_rand.push: positive [lo, hi] ranges expected"
+            steps = lambda sec: max(1, int(round(sec * self._control_freq)))      # noqa: E731  (seconds -> control steps)
+            rg.push_interval[0], rg.push_interval[1] = steps(i0), steps(i1)
+            rg.push_duration[0], rg.push_duration[1] = steps(d0), steps(d1)
+            rg.push_force[0], rg.push_force[1] = f0, f1
+        self._phys_ranges = rg
+        self._phys_mask = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._phys_rng_state = torch.zeros(2, dtype=torch.int64, device=dev)
+        self._phys_seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())      # from torch's host generator, like step_randoms
+
+    @staticmethod
+    def _check_phys_values(field, v):
+        """the rules of parc_sim_step_phys for one field, on the host (the values the env itself writes into the table)"""
+        v = torch.as_tensor(v, dtype=torch.float32).detach().cpu()
+        assert bool(torch.isfinite(v).all()), "{}: finite values expected".format(field)
+        if field in ("mass_scale", "contact_kn", "kp_scale"):
+            assert bool((v > 0).all()), "{}: positive values expected".format(field)
+        elif field in ("friction_mu", "contact_cn", "contact_ct", "kd_scale"):
+            assert bool((v >= 0).all()), "{}: non-negative values expected".format(field)
+
+    def _phys_rand(self, mask=None, tick=False):
+        rg = self._phys_ranges
+        rg.push_tick = 1 if tick else 0
+        _hip.check(_hip.lib().parc_phys_rand(_hip.stream(), self._num_envs, _hip.ptr(mask), rg, self._phys_seed, _hip.ptr(self._phys_rng_state),
+                                             _hip.ptr(self._phys_table)), "parc_phys_rand")
+
+    def _phys_push_tick(self):
+        """one control step of the push schedule (only with `physics_rand.push`), in front of the simulator launch"""
+        if self._phys_ranges is not None and self._phys_ranges.push_interval[1] > 0:
+            self._phys_rand(None, tick=True)
+
+    def get_physics_params(self):
+        """dict of [num_envs] tensors (push_force: [num_envs, 3]; push_steps_left / push_next_in: int32) that are VIEWS of the per-env
+        table: gravity, friction_mu, contact_kn, contact_cn, contact_ct, mass_scale, kp_scale, kd_scale.  None while the env steps without
+        a table (no `physics_rand` block and no setter called)."""
+        return None if self._phys_table is None else self._phys_views
+
+    def set_physics_params(self, env_ids=None, **fields):
+        """Write per-env physics parameters: each keyword is one of the fields of get_physics_params (not the push), its value a scalar
+        or a [len(env_ids)] tensor; env_ids None = all envs.  Allocates the table and switches the env to parc_sim_step_phys if it was
+        stepping without one.  Values are checked here, on the host (the captured step cannot).  A field the YAML randomises is
+        redrawn at the env's next reset."""
+        unknown = set(fields) - set(_hip_sim.PHYS_FIELDS)
+        assert not unknown, "unknown physics parameters {}".format(sorted(unknown))
+        if self._phys_table is None:
+            self._enable_physics_params()
+        for f, v in fields.items():
+            v = torch.as_tensor(v, dtype=torch.float32)
+            self._check_phys_values(f, v)
+            v = v.to(self._device)
+            if env_ids is None:
+                self._phys_views[f][:] = v
+            else:
+                self._phys_views[f][env_ids] = v
+
+    def apply_push(self, env_ids, force_xyz, num_steps):
+        """A world-frame force [3] or [len(env_ids), 3] at the root link's centre of mass for the next num_steps control steps of the
+        given envs (None = all).  Replaces a push that is still running."""
+        assert int(num_steps) >= 0
+        if self._phys_table is None:
+            self._enable_physics_params()
+        f = torch.as_tensor(force_xyz, dtype=torch.float32)
+        assert f.shape[-1] == 3 and bool(torch.isfinite(f).all()), "a finite force [.., 3] expected"
+        f = f.to(self._device)
+        if env_ids is None:
+            self._phys_views["push_force"][:] = f
+            self._phys_views["push_steps_left"][:] = int(num_steps)
+        else:
+            self._phys_views["push_force"][env_ids] = f
+            self._phys_views["push_steps_left"][env_ids] = int(num_steps)
 
     def _update_motion_targets(self):
         """DeepMimicEnv._update_motion_targets (dm_env.py:617-654) as torch ops: every env draws a candidate, only those whose
@@ -658,6 +808,8 @@ class IGParkourEnv(base_env.BaseEnv):
         info["ep_num"] = snap(self._ep_num_buf)
         info["compute_time"] = time.time() - self._start_compute_time
         info["char_contact_forces"] = snap(self._char_contact_forces)
+        if self._phys_table is not None:
+            info["physics_params"] = self._phys_views        # views of the table: a logger bins returns by parameter
         if step:
             r = dict(self._reward_term_views)
             r["total_r"] = snap(self._reward_buf)
