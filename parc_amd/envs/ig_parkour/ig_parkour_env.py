@@ -124,6 +124,7 @@ class IGParkourEnv(base_env.BaseEnv):
         # `physics_rand` block or a setter is called
         self._phys_table = None
         self._phys_ranges = None
+        self._renderer = self._frame_writer = None        # set_renderer: offscreen frames of test / record rollouts
         if env_config.get("physics_rand") is not None:
             self._enable_physics_params(env_config["physics_rand"])
         if n_mg > 0:
@@ -220,6 +221,24 @@ class IGParkourEnv(base_env.BaseEnv):
     # ------------------------------------------------------------------ env API (envs/base_env.py, envs/ig_env.py:51-98)
     def get_num_envs(self):
         return self._num_envs
+
+    def set_renderer(self, renderer, writer=None):
+        """Attach a parc_amd.render.Renderer (and a FrameWriter): every step() and every full reset() (env_ids None: the start of a rollout) from now
+        on draws one frame after the state of that step is final; restarts of single envs between steps draw none.  TEST mode only - a training rollout runs as a captured graph that this must not touch.  None detaches."""
+        if renderer is not None and self._mode != base_env.EnvMode.TEST:
+            raise RuntimeError("a renderer can only be attached in TEST mode (env.set_mode(EnvMode.TEST) first): "
+                               "the training step is captured into a graph and is not rendered")
+        self._renderer, self._frame_writer = renderer, (writer if renderer is not None else None)
+
+    def set_mode(self, mode):
+        if mode == base_env.EnvMode.TRAIN and getattr(self, "_renderer", None) is not None:
+            raise RuntimeError("detach the renderer (set_renderer(None)) before switching the env to TRAIN mode")
+        super().set_mode(mode)
+
+    def _render_frame(self):
+        frame = self._renderer.render()
+        if self._frame_writer is not None:
+            self._frame_writer.add(frame)
 
     def get_control_mode(self):
         return self._control_mode
@@ -380,6 +399,7 @@ class IGParkourEnv(base_env.BaseEnv):
 
     # ------------------------------------------------------------------ reset (ig_parkour_env.py:1012-1041, dm_env.py:656-684)
     def reset(self, env_ids=None):
+        full_reset = env_ids is None
         if env_ids is None:
             env_ids = self._all_env_ids
         env_ids = env_ids.to(torch.long)
@@ -395,6 +415,12 @@ class IGParkourEnv(base_env.BaseEnv):
             self._phys_mask[env_ids] = 1
             self._phys_rand(self._phys_mask)
         self._update_info()
+        if self._renderer is not None and full_reset:
+            # the first frame of a rollout.  The restarts of single envs between steps (reset(done_indices) after every step of a test or
+            # record rollout, mostly an empty list) draw nothing: a rollout is one frame per step, and a restarted env shows its new
+            # episode from the next step's frame on
+            self._renderer.on_full_reset()
+            self._render_frame()
         return self._obs_buf, self._info
 
     def _refresh_bodies(self, env_ids):
@@ -609,6 +635,8 @@ class IGParkourEnv(base_env.BaseEnv):
         self._update_info(step=True)
         if self._write_agent_states_flag:
             self.write_agent_states()
+        if self._renderer is not None:
+            self._render_frame()
         return self._obs_buf, self._reward_buf, self._done_buf, self._info
 
     def _sim_rows(self, act, e0, n, terrain_struct):
@@ -667,6 +695,8 @@ class IGParkourEnv(base_env.BaseEnv):
         self._update_info(step=True)
         if self._write_agent_states_flag:
             self.write_agent_states()
+        if self._renderer is not None:
+            self._render_frame()
         return self._obs_buf, self._reward_buf, self._done_buf, self._info
 
     # ------------------------------------------------------------------ per-env physics parameters and pushes (include/parc_sim.h)

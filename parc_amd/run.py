@@ -1,5 +1,7 @@
 """Launcher with the reference's run.py flags (run.py:95-164): --env_config --agent_config --mode train|test|record
 --num_envs --device --max_samples --out_model_file --int_output_dir --log_file --model_file --rand_seed --test_episodes.
+--mode test|record also take --render_dir DIR [--render_envs 0,1,...] [--render_size WxH]: frames of the rollout as
+DIR/env%04d/frame%06d.png (parc_amd/render.py); without --render_dir nothing is drawn.
 One process per GPU: under torchrun (RANK/WORLD_SIZE set) every rank takes its own device and RCCL carries the gradient
 all-reduce; --num_workers spawns local ranks like the reference does."""
 import os
@@ -42,6 +44,15 @@ def run(rank, num_procs, master_port, args):
     model_file = args.parse_string("model_file", "")
     if model_file != "":
         agent.load(model_file)
+    render_dir = args.parse_string("render_dir", "")
+    writer = None
+    if render_dir != "":
+        assert mode in ("test", "record"), "--render_dir goes with --mode test or --mode record"
+    if render_dir != "" and mp_util.is_root_proc():        # one writer per directory: the root process draws its envs, the other ranks none
+        from . import render
+        from .envs import base_env
+        env.set_mode(base_env.EnvMode.TEST)
+        writer = render.attach_from_args(env, render_dir, args.parse_string("render_envs", "0"), args.parse_string("render_size", "640x360"))
     if mode == "train":
         agent.train_model(max_samples=args.parse_int("max_samples", np.iinfo(np.int64).max), out_model_file=out_model_file,
                           int_output_dir=int_output_dir, log_file=args.parse_string("log_file", "output/log.txt"),
@@ -53,6 +64,8 @@ def run(rank, num_procs, master_port, args):
         agent.record_motions()
     else:
         raise AssertionError("Unsupported mode: {}".format(mode))
+    if writer is not None:
+        writer.close()
 
 
 def main(argv):
