@@ -32,20 +32,21 @@ class PhysRangesS(ctypes.Structure):
 
 def declare(L):
     L.parc_sim_abi.restype = c_int
+    # stream, model, terrain, n_envs, the four state tensors, env offsets, action, its two bounds, n_substeps, h
+    step = [c_vp, c_vp, _hip.TerrainS, c_int] + [c_vp] * 8 + [c_int, c_f]
+    clock = [c_vp, c_vp, c_f]                 # timestep_buf, time_buf, step_dt
     L.parc_sim_step.restype = c_int
-    L.parc_sim_step.argtypes = [c_vp, c_vp, _hip.TerrainS, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f]
+    L.parc_sim_step.argtypes = step
     L.parc_sim_step_tick.restype = c_int
-    L.parc_sim_step_tick.argtypes = [c_vp, c_vp, _hip.TerrainS, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f, c_vp, c_vp, c_f]
+    L.parc_sim_step_tick.argtypes = step + clock
     L.parc_sim_refresh_bodies.restype = c_int
     L.parc_sim_refresh_bodies.argtypes = [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]
     L.parc_sim_refresh_bodies_masked.restype = c_int
     L.parc_sim_refresh_bodies_masked.argtypes = [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.parc_sim_step_ctl.restype = c_int
-    L.parc_sim_step_ctl.argtypes = [c_vp, c_vp, _hip.TerrainS, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f, c_int, c_int,
-                                    c_vp, c_vp, c_vp, c_f]
+    L.parc_sim_step_ctl.argtypes = step + [c_int, c_int, c_vp] + clock
     L.parc_sim_step_phys.restype = c_int
-    L.parc_sim_step_phys.argtypes = [c_vp, c_vp, _hip.TerrainS, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_f, c_int, c_vp, c_int,
-                                     c_vp, c_vp, c_vp, c_f]
+    L.parc_sim_step_phys.argtypes = step + [c_int, c_vp, c_int, c_vp] + clock
     L.parc_sim_env_params_check.restype = c_int
     L.parc_sim_env_params_check.argtypes = [c_vp, c_vp, c_int]
     L.parc_phys_rand.restype = c_int

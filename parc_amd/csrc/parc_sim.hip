@@ -9,44 +9,87 @@
 #include "parc_sim_core.h"
 #include "../../include/parc_sim.h"
 
-// body-per-lane step: 16 lanes per env, 4 envs per 64-thread workgroup (parc_sim_bpl.h), pd control mode (parc_sim_step / parc_sim_step_tick,
-// and parc_sim_step_ctl with PARC_SIM_CTL_PD)
+// What one launch of the step reads and writes; the kernels fill it from their parameters, the entry points from their arguments.
+namespace {
+struct StepArgs {
+    const parc_sim_model_t *model;
+    parc_terrain_t terrain;
+    int n_envs;
+    float *root_state, *dof_state, *rigid_body_state, *contact_forces;
+    const float *env_offsets, *action, *act_lo, *act_hi;
+    int n_sub;
+    float h;
+    int32_t *timestep;                      // the env's clock (both or neither): IGEnv._update_time rides in the launch
+    float *time_buf;
+    float step_dt;
+    int hold;                               // substeps per hold (modes other than pd)
+    float *dof_torque;                      // [N,D] torque of the last hold (torque / pd_exp / pd_1d), optional
+    parc_sim_env_params_t *env_params;      // [N] per-env physics parameters (PHYS)
+};
+}  // namespace
+
+// The body-per-lane step of one workgroup: 16 lanes per env, 4 envs per 64-thread workgroup (parc_sim_bpl.h).  MODE: PARC_SIM_CTL_*, in
+// holds of `hold` substeps.  PHYS: the rows of the workgroup's four envs are staged in LDS next to the model (one 64-byte row per 16-lane
+// group: lane b copies word b), where the sweeps read each value at its point of use; the push counter of a real env goes down by one
+// per launch.
+template <int MODE, bool PHYS>
+__device__ __forceinline__ void step_workgroup(const StepArgs a) {
+    using namespace parc_sim_bpl;
+    __shared__ float lds[BPL_EPB][BPL_G * BPL_CONTRIB];
+    __shared__ float ccache[64][BPL_CC_SLOTS * BPL_CC_FLOATS + 1];     // +1: odd row stride against bank conflicts
+    const int g = threadIdx.x / BPL_G, b = threadIdx.x % BPL_G;
+    const int e = min((int)blockIdx.x * BPL_EPB + g, a.n_envs - 1);    // tail groups recompute the last env (same values)
+    // the model (4.9 KB of per-body / per-dof / per-sphere constants, read ~70 times per lane and substep) staged in LDS once per
+    // workgroup: 100.9 -> 97.2 us per 4096-env step (profiles/r04_sim_step_variants.txt)
+    __shared__ parc_sim_model_t s_model;
+    // the envs' rows.  Only `if constexpr (PHYS)` code names s_ep, so without a table it is never emitted and takes no LDS: the 34552
+    // bytes per block of the kernels without a table (34816 with one) depend on that - check both after touching this function
+    __shared__ parc_sim_env_params_t s_ep[BPL_EPB];
+    const parc_sim_env_params_t *ep = nullptr;
+    {
+        static_assert(sizeof(parc_sim_model_t) % 4 == 0, "copied as 32-bit words");
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(a.model);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(&s_model);
+        for (unsigned i = threadIdx.x; i < sizeof(parc_sim_model_t) / 4; i += 64) dst[i] = src[i];
+        if constexpr (PHYS) {
+            static_assert(sizeof(parc_sim_env_params_t) == 4 * BPL_G, "one word of the row per lane of the env's group");
+            reinterpret_cast<uint32_t *>(&s_ep[g])[b] = reinterpret_cast<const uint32_t *>(a.env_params + e)[b];
+            ep = &s_ep[g];
+        }
+        __syncthreads();
+    }
+    const parc_sim_model_t &m = s_model;
+    const int B = m.num_bodies, D = m.dof_size;
+    step_lane<MODE, PHYS>(m, a.terrain, b, a.root_state + 13 * (size_t)e, a.dof_state + 2 * (size_t)D * e,
+                          a.rigid_body_state + 13 * (size_t)B * e, a.contact_forces + 3 * (size_t)B * e, a.env_offsets + 3 * (size_t)e,
+                          a.action + (size_t)D * e, a.act_lo, a.act_hi, a.n_sub, a.h, lds[g], ccache[threadIdx.x], a.hold,
+                          a.dof_torque ? a.dof_torque + (size_t)D * e : nullptr, ep);
+    if (b == 0 && (int)blockIdx.x * BPL_EPB + g < a.n_envs) {
+        if constexpr (PHYS) {
+            const int left = ep->push_steps_left;
+            if (left > 0) a.env_params[e].push_steps_left = left - 1;
+        }
+        // IGEnv._update_time (ig_env.py:862-865) for callers that ask for it: the env's step counter and clock advance with the simulator
+        if (a.timestep) {
+            const int ts = a.timestep[e] + 1;
+            a.timestep[e] = ts;
+            a.time_buf[e] = (float)ts * a.step_dt;
+        }
+    }
+}
+
+// pd control mode without a table: parc_sim_step / parc_sim_step_tick, and parc_sim_step_ctl with PARC_SIM_CTL_PD
 __global__ __launch_bounds__(64) void sim_step_bpl_kernel(const parc_sim_model_t *__restrict__ model, parc_terrain_t ter, int n_envs,
                                                           float *root_state, float *dof_state, float *rigid_body_state,
                                                           float *contact_forces, const float *__restrict__ env_offsets,
                                                           const float *__restrict__ action, const float *__restrict__ act_lo,
                                                           const float *__restrict__ act_hi, int n_sub, float h, int32_t *timestep,
                                                           float *time_buf, float step_dt) {
-    using namespace parc_sim_bpl;
-    __shared__ float lds[BPL_EPB][BPL_G * BPL_CONTRIB];
-    __shared__ float ccache[64][BPL_CC_SLOTS * BPL_CC_FLOATS + 1];     // +1: odd row stride against bank conflicts
-    const int g = threadIdx.x / BPL_G, b = threadIdx.x % BPL_G;
-    const int e = min((int)blockIdx.x * BPL_EPB + g, n_envs - 1);      // tail groups recompute the last env (same values)
-    // the model (4.9 KB of per-body / per-dof / per-sphere constants, read ~70 times per lane and substep) staged in LDS once per
-    // workgroup: 100.9 -> 97.2 us per 4096-env step (profiles/r04_sim_step_variants.txt)
-    __shared__ parc_sim_model_t s_model;
-    {
-        static_assert(sizeof(parc_sim_model_t) % 4 == 0, "copied as 32-bit words");
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(model);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(&s_model);
-        for (unsigned i = threadIdx.x; i < sizeof(parc_sim_model_t) / 4; i += 64) dst[i] = src[i];
-        __syncthreads();
-    }
-    const parc_sim_model_t &m = s_model;
-    const int B = m.num_bodies, D = m.dof_size;
-    step_lane(m, ter, b, root_state + 13 * (size_t)e, dof_state + 2 * (size_t)D * e, rigid_body_state + 13 * (size_t)B * e,
-              contact_forces + 3 * (size_t)B * e, env_offsets + 3 * (size_t)e, action + (size_t)D * e, act_lo, act_hi, n_sub, h, lds[g],
-              ccache[threadIdx.x]);
-    // IGEnv._update_time (ig_env.py:862-865) for callers that ask for it: the env's step counter and clock advance with the simulator
-    if (timestep && b == 0 && (int)blockIdx.x * BPL_EPB + g < n_envs) {
-        const int ts = timestep[e] + 1;
-        timestep[e] = ts;
-        time_buf[e] = (float)ts * step_dt;
-    }
+    step_workgroup<PARC_SIM_CTL_PD, false>(StepArgs{model, ter, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets,
+                                                    action, act_lo, act_hi, n_sub, h, timestep, time_buf, step_dt, 1, nullptr, nullptr});
 }
 
-// the other control modes (parc_sim_step_ctl): the same workgroup layout, holds of `hold` substeps, the torque of the last hold to
-// dof_torque [N,D] (optional).  (A separate kernel body, so that the pd kernel's code stays what it was.)
+// the other control modes without a table (parc_sim_step_ctl)
 template <int MODE>
 __global__ __launch_bounds__(64) void sim_step_bpl_ctl_kernel(const parc_sim_model_t *__restrict__ model, parc_terrain_t ter, int n_envs,
                                                               float *root_state, float *dof_state, float *rigid_body_state,
@@ -54,37 +97,11 @@ __global__ __launch_bounds__(64) void sim_step_bpl_ctl_kernel(const parc_sim_mod
                                                               const float *__restrict__ action, const float *__restrict__ act_lo,
                                                               const float *__restrict__ act_hi, int n_sub, float h, int32_t *timestep,
                                                               float *time_buf, float step_dt, int hold, float *dof_torque) {
-    using namespace parc_sim_bpl;
-    __shared__ float lds[BPL_EPB][BPL_G * BPL_CONTRIB];
-    __shared__ float ccache[64][BPL_CC_SLOTS * BPL_CC_FLOATS + 1];     // +1: odd row stride against bank conflicts
-    const int g = threadIdx.x / BPL_G, b = threadIdx.x % BPL_G;
-    const int e = min((int)blockIdx.x * BPL_EPB + g, n_envs - 1);      // tail groups recompute the last env (same values)
-    // the model staged in LDS once per workgroup, as in sim_step_bpl_kernel
-    __shared__ parc_sim_model_t s_model;
-    {
-        static_assert(sizeof(parc_sim_model_t) % 4 == 0, "copied as 32-bit words");
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(model);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(&s_model);
-        for (unsigned i = threadIdx.x; i < sizeof(parc_sim_model_t) / 4; i += 64) dst[i] = src[i];
-        __syncthreads();
-    }
-    const parc_sim_model_t &m = s_model;
-    const int B = m.num_bodies, D = m.dof_size;
-    step_lane<MODE>(m, ter, b, root_state + 13 * (size_t)e, dof_state + 2 * (size_t)D * e, rigid_body_state + 13 * (size_t)B * e,
-                    contact_forces + 3 * (size_t)B * e, env_offsets + 3 * (size_t)e, action + (size_t)D * e, act_lo, act_hi, n_sub, h, lds[g],
-                    ccache[threadIdx.x], hold, dof_torque ? dof_torque + (size_t)D * e : nullptr);
-    // IGEnv._update_time (ig_env.py:862-865) for callers that ask for it: the env's step counter and clock advance with the simulator
-    if (timestep && b == 0 && (int)blockIdx.x * BPL_EPB + g < n_envs) {
-        const int ts = timestep[e] + 1;
-        timestep[e] = ts;
-        time_buf[e] = (float)ts * step_dt;
-    }
+    step_workgroup<MODE, false>(StepArgs{model, ter, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action,
+                                         act_lo, act_hi, n_sub, h, timestep, time_buf, step_dt, hold, dof_torque, nullptr});
 }
 
-// the step with per-env physics parameters (parc_sim_step_phys), every control mode: the ctl kernel's layout plus the rows of the
-// workgroup's four envs staged in LDS next to the model (one 64-byte row per 16-lane group: lane b copies word b), where the sweeps read
-// each value at its point of use.  The push counter of a real env goes down by one per launch.  (A separate kernel body again: the
-// kernels without a table keep their code.)
+// every control mode with per-env physics parameters (parc_sim_step_phys)
 template <int MODE>
 __global__ __launch_bounds__(64) void sim_step_bpl_phys_kernel(const parc_sim_model_t *__restrict__ model, parc_terrain_t ter, int n_envs,
                                                                float *root_state, float *dof_state, float *rigid_body_state,
@@ -93,37 +110,8 @@ __global__ __launch_bounds__(64) void sim_step_bpl_phys_kernel(const parc_sim_mo
                                                                const float *__restrict__ act_hi, int n_sub, float h, int32_t *timestep,
                                                                float *time_buf, float step_dt, int hold, float *dof_torque,
                                                                parc_sim_env_params_t *env_params) {
-    using namespace parc_sim_bpl;
-    __shared__ float lds[BPL_EPB][BPL_G * BPL_CONTRIB];
-    __shared__ float ccache[64][BPL_CC_SLOTS * BPL_CC_FLOATS + 1];     // +1: odd row stride against bank conflicts
-    const int g = threadIdx.x / BPL_G, b = threadIdx.x % BPL_G;
-    const int e = min((int)blockIdx.x * BPL_EPB + g, n_envs - 1);      // tail groups recompute the last env (same values)
-    __shared__ parc_sim_model_t s_model;
-    __shared__ parc_sim_env_params_t s_ep[BPL_EPB];
-    {
-        static_assert(sizeof(parc_sim_model_t) % 4 == 0, "copied as 32-bit words");
-        static_assert(sizeof(parc_sim_env_params_t) == 4 * BPL_G, "one word of the row per lane of the env's group");
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(model);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(&s_model);
-        for (unsigned i = threadIdx.x; i < sizeof(parc_sim_model_t) / 4; i += 64) dst[i] = src[i];
-        reinterpret_cast<uint32_t *>(&s_ep[g])[b] = reinterpret_cast<const uint32_t *>(env_params + e)[b];
-        __syncthreads();
-    }
-    const parc_sim_model_t &m = s_model;
-    const int B = m.num_bodies, D = m.dof_size;
-    step_lane<MODE, true>(m, ter, b, root_state + 13 * (size_t)e, dof_state + 2 * (size_t)D * e, rigid_body_state + 13 * (size_t)B * e,
-                          contact_forces + 3 * (size_t)B * e, env_offsets + 3 * (size_t)e, action + (size_t)D * e, act_lo, act_hi, n_sub, h,
-                          lds[g], ccache[threadIdx.x], hold, dof_torque ? dof_torque + (size_t)D * e : nullptr, &s_ep[g]);
-    if (b == 0 && (int)blockIdx.x * BPL_EPB + g < n_envs) {
-        const int left = s_ep[g].push_steps_left;
-        if (left > 0) env_params[e].push_steps_left = left - 1;
-        // IGEnv._update_time, as in the other step kernels
-        if (timestep) {
-            const int ts = timestep[e] + 1;
-            timestep[e] = ts;
-            time_buf[e] = (float)ts * step_dt;
-        }
-    }
+    step_workgroup<MODE, true>(StepArgs{model, ter, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action,
+                                        act_lo, act_hi, n_sub, h, timestep, time_buf, step_dt, hold, dof_torque, env_params});
 }
 
 // the rows' rules (parc_sim_core.h env_params_valid): *bad <- 1 if any row breaks one
@@ -166,43 +154,57 @@ __global__ __launch_bounds__(64) void sim_refresh_bpl_kernel(const parc_sim_mode
 
 static_assert(PARC_SIM_MAX_BODIES <= BPL_G, "one body per lane: a 16-lane group holds one env");
 
-static int sim_step_impl(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state,
-                         float *dof_state, float *rigid_body_state, float *contact_forces, const float *env_offsets, const float *action,
-                         const float *action_low, const float *action_high, int n_substeps, float h, int32_t *timestep, float *time_buf,
-                         float step_dt) {
-    if (!model || n_envs < 0 || n_substeps <= 0 || !(h > 0.f) || !terrain.hf) return PARC_EINVAL;
-    if (n_envs == 0) return PARC_OK;
-    hipLaunchKernelGGL(sim_step_bpl_kernel, dim3((n_envs + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, model, terrain, n_envs,
-                       root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h,
-                       timestep, time_buf, step_dt);
-    hipError_t e1 = hipGetLastError();
-    return e1 == hipSuccess ? PARC_OK : (int)e1;
+// PARC_OK, or the error of the launch just issued
+static int launch_rc() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PARC_OK : (int)e;
+}
+
+// The argument rules that the step entry points share, checked before any HIP call
+static bool step_args_ok(const StepArgs &a, int mode) {
+    if (!a.model || a.n_envs < 0 || a.n_sub <= 0 || !(a.h > 0.f) || !a.terrain.hf) return false;
+    if (mode < PARC_SIM_CTL_PD || mode > PARC_SIM_CTL_PD_1D) return false;
+    if (a.hold <= 0 || a.n_sub % a.hold != 0) return false;
+    if ((a.timestep == nullptr) != (a.time_buf == nullptr)) return false;
+    return !(a.dof_torque && (mode == PARC_SIM_CTL_PD || mode == PARC_SIM_CTL_VEL));
+}
+
+// The launch of checked arguments: the table's kernel if there is a table, else the pd kernel or the mode's
+static int launch_step(void *stream, const StepArgs &a, int mode, bool table) {
+    if (a.n_envs == 0) return PARC_OK;
+    auto launch = [&](auto kernel, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3((a.n_envs + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, a.model, a.terrain, a.n_envs,
+                           a.root_state, a.dof_state, a.rigid_body_state, a.contact_forces, a.env_offsets, a.action, a.act_lo, a.act_hi, a.n_sub,
+                           a.h, a.timestep, a.time_buf, a.step_dt, more...);
+    };
+    parc_sim::ctl_dispatch(mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        if (table)
+            launch(sim_step_bpl_phys_kernel<MODE>, a.hold, a.dof_torque, a.env_params);
+        else if constexpr (MODE == PARC_SIM_CTL_PD)
+            launch(sim_step_bpl_kernel);
+        else
+            launch(sim_step_bpl_ctl_kernel<MODE>, a.hold, a.dof_torque);
+    });
+    return launch_rc();
 }
 
 extern "C" int parc_sim_step(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state,
                              float *dof_state, float *rigid_body_state, float *contact_forces, const float *env_offsets,
                              const float *action, const float *action_low, const float *action_high, int n_substeps, float h) {
-    return sim_step_impl(stream, model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low,
-                         action_high, n_substeps, h, nullptr, nullptr, 0.f);
+    const StepArgs a{model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low,
+                     action_high, n_substeps, h, nullptr, nullptr, 0.f, 1, nullptr, nullptr};
+    return step_args_ok(a, PARC_SIM_CTL_PD) ? launch_step(stream, a, PARC_SIM_CTL_PD, false) : PARC_EINVAL;
 }
 
 extern "C" int parc_sim_step_tick(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state,
                                   float *dof_state, float *rigid_body_state, float *contact_forces, const float *env_offsets,
                                   const float *action, const float *action_low, const float *action_high, int n_substeps, float h,
                                   int32_t *timestep_buf, float *time_buf, float step_dt) {
-    if (!timestep_buf || !time_buf) return PARC_EINVAL;
-    return sim_step_impl(stream, model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low,
-                         action_high, n_substeps, h, timestep_buf, time_buf, step_dt);
-}
-
-template <int MODE>
-static void launch_ctl(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state, float *dof_state,
-                       float *rigid_body_state, float *contact_forces, const float *env_offsets, const float *action, const float *action_low,
-                       const float *action_high, int n_substeps, float h, int32_t *timestep, float *time_buf, float step_dt, int hold,
-                       float *dof_torque) {
-    hipLaunchKernelGGL(sim_step_bpl_ctl_kernel<MODE>, dim3((n_envs + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, model, terrain,
-                       n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps,
-                       h, timestep, time_buf, step_dt, hold, dof_torque);
+    const StepArgs a{model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low,
+                     action_high, n_substeps, h, timestep_buf, time_buf, step_dt, 1, nullptr, nullptr};
+    if (!timestep_buf || !step_args_ok(a, PARC_SIM_CTL_PD)) return PARC_EINVAL;
+    return launch_step(stream, a, PARC_SIM_CTL_PD, false);
 }
 
 extern "C" int parc_sim_step_ctl(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state,
@@ -210,33 +212,9 @@ extern "C" int parc_sim_step_ctl(void *stream, const parc_sim_model_t *model, pa
                                  const float *action, const float *action_low, const float *action_high, int n_substeps, float h,
                                  int substeps_per_hold, int control_mode, float *dof_torque, int32_t *timestep_buf, float *time_buf,
                                  float step_dt) {
-    if (control_mode < PARC_SIM_CTL_PD || control_mode > PARC_SIM_CTL_PD_1D) return PARC_EINVAL;
-    if (substeps_per_hold <= 0 || n_substeps <= 0 || n_substeps % substeps_per_hold != 0) return PARC_EINVAL;
-    if ((timestep_buf == nullptr) != (time_buf == nullptr)) return PARC_EINVAL;
-    if (dof_torque && (control_mode == PARC_SIM_CTL_PD || control_mode == PARC_SIM_CTL_VEL)) return PARC_EINVAL;
-    if (control_mode == PARC_SIM_CTL_PD)
-        return sim_step_impl(stream, model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action,
-                             action_low, action_high, n_substeps, h, timestep_buf, time_buf, step_dt);
-    if (!model || n_envs < 0 || !(h > 0.f) || !terrain.hf) return PARC_EINVAL;
-    if (n_envs == 0) return PARC_OK;
-    auto launch = control_mode == PARC_SIM_CTL_VEL      ? launch_ctl<PARC_SIM_CTL_VEL>
-                  : control_mode == PARC_SIM_CTL_TORQUE ? launch_ctl<PARC_SIM_CTL_TORQUE>
-                  : control_mode == PARC_SIM_CTL_PD_EXP ? launch_ctl<PARC_SIM_CTL_PD_EXP>
-                                                        : launch_ctl<PARC_SIM_CTL_PD_1D>;
-    launch(stream, model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high,
-           n_substeps, h, timestep_buf, time_buf, step_dt, substeps_per_hold, dof_torque);
-    hipError_t e1 = hipGetLastError();
-    return e1 == hipSuccess ? PARC_OK : (int)e1;
-}
-
-template <int MODE>
-static void launch_phys(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state, float *dof_state,
-                        float *rigid_body_state, float *contact_forces, const float *env_offsets, const float *action, const float *action_low,
-                        const float *action_high, int n_substeps, float h, int32_t *timestep, float *time_buf, float step_dt, int hold,
-                        float *dof_torque, parc_sim_env_params_t *env_params) {
-    hipLaunchKernelGGL(sim_step_bpl_phys_kernel<MODE>, dim3((n_envs + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, model, terrain,
-                       n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps,
-                       h, timestep, time_buf, step_dt, hold, dof_torque, env_params);
+    const StepArgs a{model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low,
+                     action_high, n_substeps, h, timestep_buf, time_buf, step_dt, substeps_per_hold, dof_torque, nullptr};
+    return step_args_ok(a, control_mode) ? launch_step(stream, a, control_mode, false) : PARC_EINVAL;
 }
 
 // The verdict cell of phys_check_kernel: one word of pinned, portable host memory that the device writes directly, allocated at the first
@@ -260,8 +238,9 @@ extern "C" int parc_sim_env_params_check(void *stream, const parc_sim_env_params
     }
     *g_check_cell = 0;
     hipLaunchKernelGGL(phys_check_kernel, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, env_params, n_envs, g_check_cell);
-    hipError_t e1 = hipGetLastError();
-    if (e1 == hipSuccess) e1 = hipStreamSynchronize((hipStream_t)stream);
+    const int rc = launch_rc();
+    if (rc != PARC_OK) return rc;
+    const hipError_t e1 = hipStreamSynchronize((hipStream_t)stream);
     if (e1 != hipSuccess) return (int)e1;
     return *g_check_cell ? PARC_EINVAL : PARC_OK;
 }
@@ -271,32 +250,22 @@ extern "C" int parc_sim_step_phys(void *stream, const parc_sim_model_t *model, p
                                   const float *action, const float *action_low, const float *action_high, int n_substeps, float h,
                                   int substeps_per_hold, parc_sim_env_params_t *env_params, int control_mode, float *dof_torque,
                                   int32_t *timestep_buf, float *time_buf, float step_dt) {
-    if (!env_params) return PARC_EINVAL;
-    if (control_mode < PARC_SIM_CTL_PD || control_mode > PARC_SIM_CTL_PD_1D) return PARC_EINVAL;
-    if (substeps_per_hold <= 0 || n_substeps <= 0 || n_substeps % substeps_per_hold != 0) return PARC_EINVAL;
-    if ((timestep_buf == nullptr) != (time_buf == nullptr)) return PARC_EINVAL;
-    if (dof_torque && (control_mode == PARC_SIM_CTL_PD || control_mode == PARC_SIM_CTL_VEL)) return PARC_EINVAL;
-    if (!model || n_envs < 0 || !(h > 0.f) || !terrain.hf) return PARC_EINVAL;
-    if (n_envs == 0) return PARC_OK;
-    // the rows' rules: checked in front of the step unless the stream is being captured (nothing can be waited for there)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
-        (void)hipGetLastError();
-        cap = hipStreamCaptureStatusNone;
+    const StepArgs a{model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low,
+                     action_high, n_substeps, h, timestep_buf, time_buf, step_dt, substeps_per_hold, dof_torque, env_params};
+    if (!env_params || !step_args_ok(a, control_mode)) return PARC_EINVAL;
+    if (n_envs > 0) {
+        // the rows' rules: checked in front of the step unless the stream is being captured (nothing can be waited for there)
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
+            (void)hipGetLastError();
+            cap = hipStreamCaptureStatusNone;
+        }
+        if (cap == hipStreamCaptureStatusNone) {
+            const int rc = parc_sim_env_params_check(stream, env_params, n_envs);
+            if (rc != PARC_OK) return rc;
+        }
     }
-    if (cap == hipStreamCaptureStatusNone) {
-        const int rc = parc_sim_env_params_check(stream, env_params, n_envs);
-        if (rc != PARC_OK) return rc;
-    }
-    auto launch = control_mode == PARC_SIM_CTL_PD       ? launch_phys<PARC_SIM_CTL_PD>
-                  : control_mode == PARC_SIM_CTL_VEL    ? launch_phys<PARC_SIM_CTL_VEL>
-                  : control_mode == PARC_SIM_CTL_TORQUE ? launch_phys<PARC_SIM_CTL_TORQUE>
-                  : control_mode == PARC_SIM_CTL_PD_EXP ? launch_phys<PARC_SIM_CTL_PD_EXP>
-                                                        : launch_phys<PARC_SIM_CTL_PD_1D>;
-    launch(stream, model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high,
-           n_substeps, h, timestep_buf, time_buf, step_dt, substeps_per_hold, dof_torque, env_params);
-    hipError_t e1 = hipGetLastError();
-    return e1 == hipSuccess ? PARC_OK : (int)e1;
+    return launch_step(stream, a, control_mode, true);
 }
 
 // =============================================================================================
@@ -405,30 +374,30 @@ extern "C" int parc_phys_rand(void *stream, int n_envs, const int32_t *reset_mas
     if (n_envs == 0) return PARC_OK;
     hipLaunchKernelGGL(phys_rand_kernel, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_envs, reset_mask, g, seed, rng_state,
                        env_params);
-    hipError_t e1 = hipGetLastError();
-    return e1 == hipSuccess ? PARC_OK : (int)e1;
+    return launch_rc();
+}
+
+// the refresh of n rows: a list of envs, a mask over the envs, or neither
+static int launch_refresh(void *stream, const parc_sim_model_t *model, int n, const int64_t *env_ids, const int32_t *mask,
+                          const float *root_state, const float *dof_state, float *rigid_body_state, float *contact_forces) {
+    if (n == 0) return PARC_OK;
+    hipLaunchKernelGGL(sim_refresh_bpl_kernel, dim3((n + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, model, n, env_ids, mask,
+                       root_state, dof_state, rigid_body_state, contact_forces);
+    return launch_rc();
 }
 
 extern "C" int parc_sim_refresh_bodies(void *stream, const parc_sim_model_t *model, int n_envs, const int64_t *env_ids, int n_sel,
                                        const float *root_state, const float *dof_state, float *rigid_body_state, float *contact_forces) {
-    if (!model || n_envs < 0) return PARC_EINVAL;
-    int n = env_ids ? n_sel : n_envs;
-    if (n <= 0) return n == 0 ? PARC_OK : PARC_EINVAL;
-    hipLaunchKernelGGL(sim_refresh_bpl_kernel, dim3((n + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, model, n, env_ids,
-                       (const int32_t *)nullptr, root_state, dof_state, rigid_body_state, contact_forces);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    const int n = env_ids ? n_sel : n_envs;
+    if (!model || n_envs < 0 || n < 0) return PARC_EINVAL;
+    return launch_refresh(stream, model, n, env_ids, nullptr, root_state, dof_state, rigid_body_state, contact_forces);
 }
 
 extern "C" int parc_sim_refresh_bodies_masked(void *stream, const parc_sim_model_t *model, int n_envs, const int32_t *mask,
                                               const float *root_state, const float *dof_state, float *rigid_body_state,
                                               float *contact_forces) {
     if (!model || n_envs < 0 || !mask) return PARC_EINVAL;
-    if (n_envs == 0) return PARC_OK;
-    hipLaunchKernelGGL(sim_refresh_bpl_kernel, dim3((n_envs + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, model, n_envs,
-                       (const int64_t *)nullptr, mask, root_state, dof_state, rigid_body_state, contact_forces);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    return launch_refresh(stream, model, n_envs, nullptr, mask, root_state, dof_state, rigid_body_state, contact_forces);
 }
 
 extern "C" int parc_sim_abi(void) { return 1; }

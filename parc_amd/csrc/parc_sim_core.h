@@ -24,6 +24,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/parc_sim.h"
 
 #if defined(__HIPCC__)
@@ -1065,6 +1067,20 @@ PARC_HD void env_step(const parc_sim_model_t &m, const parc_terrain_t &ter, cons
                       int n_sub, float h, Scratch &s) {
     env_step_ctl<PARC_SIM_CTL_PD>(m, ter, env_offset, root_state, dof_state, rigid_body_state, contact_forces, action, act_lo, act_hi, n_sub, h,
                                   s, 1, nullptr);
+}
+
+// Host side: the control mode as a compile-time constant.  f(std::integral_constant<int, M>{}) for a mode M in range (true), nothing for
+// any other (false).  The one place that lists PARC_SIM_CTL_* to pick a template instantiation: the device launches and the host builds.
+template <class F>
+inline bool ctl_dispatch(int mode, F &&f) {
+    switch (mode) {
+    case PARC_SIM_CTL_PD: f(std::integral_constant<int, PARC_SIM_CTL_PD>{}); return true;
+    case PARC_SIM_CTL_VEL: f(std::integral_constant<int, PARC_SIM_CTL_VEL>{}); return true;
+    case PARC_SIM_CTL_TORQUE: f(std::integral_constant<int, PARC_SIM_CTL_TORQUE>{}); return true;
+    case PARC_SIM_CTL_PD_EXP: f(std::integral_constant<int, PARC_SIM_CTL_PD_EXP>{}); return true;
+    case PARC_SIM_CTL_PD_1D: f(std::integral_constant<int, PARC_SIM_CTL_PD_1D>{}); return true;
+    default: return false;
+    }
 }
 
 }  // namespace parc_sim

@@ -613,16 +613,7 @@ class IGParkourEnv(base_env.BaseEnv):
         # timestep += 1, time = timestep * dt) rides in the same launch
         if self._phys_table is not None:
             self._phys_push_tick()
-            self._sim_rows(act, 0, self._num_envs, c._terrain_struct)
-        elif self._ctl != _hip_sim.CONTROL_MODES["pd"]:
-            self._sim_rows(act, 0, self._num_envs, c._terrain_struct)
-        else:
-            L = _hip.lib()
-            sim_args = (_hip.stream(), self._sim_model.device_ptr(self._device), c._terrain_struct, self._num_envs, _hip.ptr(c.root_state),
-                        _hip.ptr(c.dof_state), _hip.ptr(c.rigid_body_state), _hip.ptr(c.contact_forces), _hip.ptr(c.env_offsets), _hip.ptr(act),
-                        _hip.ptr(self._action_bound_low), _hip.ptr(self._action_bound_high), self._sim_steps * self._substeps, self._sim_h)
-            _hip.check(L.parc_sim_step_tick(*sim_args, _hip.ptr(self._timestep_buf), _hip.ptr(self._time_buf), float(self._timestep)),
-                       "parc_sim_step_tick")
+        self._sim_rows(act, 0, self._num_envs, c._terrain_struct)
         # _update_misc (incl. the xy target resample) / _update_observations / _update_reward / _update_done in one launch
         self._draw_step_uniforms()      # all uniforms of this step and of the restarts that follow it (tracker_core.rand_pool)
         # (the reference STATE - ref_* buffers - rides in the fail-rate launch below: nothing in the fused launch reads it)
@@ -644,29 +635,20 @@ class IGParkourEnv(base_env.BaseEnv):
         c = self._core
         B, D = self._cfg.num_bodies, self._cfg.dof_size
         p = _hip.ptr
+        L = _hip.lib()
+        args = (_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]), p(c.dof_state[e0 * D:]),
+                p(c.rigid_body_state[e0 * B:]), p(c.contact_forces[e0 * B:]), p(c.env_offsets[e0:]), p(act[e0:]), p(self._action_bound_low),
+                p(self._action_bound_high), self._sim_steps * self._substeps, self._sim_h)
+        torque = p(self._dof_torque[e0:]) if self._dof_torque is not None else None
+        clock = (p(self._timestep_buf[e0:]), p(self._time_buf[e0:]), float(self._timestep))
         if self._phys_table is not None:
             # per-env physics parameters: every control mode, pd included, through the table's kernel
-            _hip.check(_hip.lib().parc_sim_step_phys(_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]),
-                                                     p(c.dof_state[e0 * D:]), p(c.rigid_body_state[e0 * B:]), p(c.contact_forces[e0 * B:]),
-                                                     p(c.env_offsets[e0:]), p(act[e0:]), p(self._action_bound_low), p(self._action_bound_high),
-                                                     self._sim_steps * self._substeps, self._sim_h, self._substeps, p(self._phys_table[e0:]),
-                                                     self._ctl, p(self._dof_torque[e0:]) if self._dof_torque is not None else None,
-                                                     p(self._timestep_buf[e0:]), p(self._time_buf[e0:]), float(self._timestep)), "parc_sim_step_phys")
-            return
-        if self._ctl != _hip_sim.CONTROL_MODES["pd"]:
+            _hip.check(L.parc_sim_step_phys(*args, self._substeps, p(self._phys_table[e0:]), self._ctl, torque, *clock), "parc_sim_step_phys")
+        elif self._ctl != _hip_sim.CONTROL_MODES["pd"]:
             # the other control modes: holds of `substeps` (one gym.simulate each); pd_exp / pd_1d ignore the bounds (unclipped targets)
-            _hip.check(_hip.lib().parc_sim_step_ctl(_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]),
-                                                    p(c.dof_state[e0 * D:]), p(c.rigid_body_state[e0 * B:]), p(c.contact_forces[e0 * B:]),
-                                                    p(c.env_offsets[e0:]), p(act[e0:]), p(self._action_bound_low), p(self._action_bound_high),
-                                                    self._sim_steps * self._substeps, self._sim_h, self._substeps, self._ctl,
-                                                    p(self._dof_torque[e0:]) if self._dof_torque is not None else None,
-                                                    p(self._timestep_buf[e0:]), p(self._time_buf[e0:]), float(self._timestep)), "parc_sim_step_ctl")
-            return
-        _hip.check(_hip.lib().parc_sim_step_tick(_hip.stream(), self._sim_model.device_ptr(self._device), terrain_struct, n, p(c.root_state[e0:]),
-                                                 p(c.dof_state[e0 * D:]), p(c.rigid_body_state[e0 * B:]), p(c.contact_forces[e0 * B:]),
-                                                 p(c.env_offsets[e0:]), p(act[e0:]), p(self._action_bound_low), p(self._action_bound_high),
-                                                 self._sim_steps * self._substeps, self._sim_h, p(self._timestep_buf[e0:]), p(self._time_buf[e0:]),
-                                                 float(self._timestep)), "parc_sim_step_tick")
+            _hip.check(L.parc_sim_step_ctl(*args, self._substeps, self._ctl, torque, *clock), "parc_sim_step_ctl")
+        else:
+            _hip.check(L.parc_sim_step_tick(*args, *clock), "parc_sim_step_tick")
 
     def _step_sub_envs(self, act):
         """The same step when rows are split between the two sub-envs: every launch once per sub-env on its rows, in the reference's

@@ -199,3 +199,62 @@ def test_mixed_rows_step_in_pd_exp():
     tq = env.get_dof_torque()
     assert torch.isfinite(tq).all()
     assert tq[:n_dm].abs().sum() > 0 and tq[n_dm:].abs().sum() > 0
+
+
+def test_tail_group_and_epilogue_in_every_step_entry(humanoid):
+    """The workgroup prologue and epilogue that the step kernels share, through parc_sim_step_tick, parc_sim_step_ctl (torque, with clock
+    buffers and a torque output) and parc_sim_step_phys (pd, rows with push_steps_left = 2): the humanoid on flat ground at 5 envs (two
+    workgroups, the second with one live env and three clamped groups) and at 8 envs with the same first five rows, two steps.  Rows
+    0-4 are bit-identical between the two launches, the clock and the push counter move by exactly one per step, and the 5-env launches
+    leave the three guard rows past row 4 of every tensor, clock buffer and table as they were."""
+    import sim_phys
+    from parc_amd import _hip
+    _, sm = humanoid
+    D, B, R, LIVE, DT = int(sm.struct.dof_size), int(sm.struct.num_bodies), 8, 5, 1.0 / 30.0
+    rng = np.random.default_rng(5)
+    root = np.zeros((R, 13), np.float32)
+    root[:, 2], root[:, 6] = 0.95, 1.0
+    dof = np.zeros((R, D, 2), np.float32)
+    dof[..., 0] = rng.normal(0.0, 0.2, (R, D))
+    acts = [torch.tensor(rng.normal(0.0, 0.5, (R, D)).astype(np.float32), device=DEV) for _ in range(2)]
+    rows = sim_phys.neutral_rows(sm.struct, R)
+    rows["push_force"], rows["push_steps_left"] = (50.0, 20.0, 0.0), 2
+    left = sim_phys.ROW.fields["push_steps_left"][1] // 4          # the counter's word of the row
+    model = torch.frombuffer(bytearray(bytes(sm.struct)), dtype=torch.uint8).to(DEV)
+    hf = torch.zeros((20, 20), device=DEV)
+    ter = _hip.terrain_struct(hf, (-4.0, -4.0), (0.4, 0.4))
+    lo, hi, offsets = torch.full((D,), -10.0, device=DEV), torch.full((D,), 10.0, device=DEV), torch.zeros((R, 3), device=DEV)
+    ts0 = torch.arange(7, 7 + 3 * R, 3, dtype=torch.int32, device=DEV)
+    p, L, guard = _hip.ptr, _hip.lib(), {torch.int32: -12345, torch.float32: -777.25}
+
+    def run(entry, n):
+        """two steps of `entry` on n envs, rows n.. of every output holding a sentinel; the outputs after each step"""
+        t = {"root": torch.tensor(root, device=DEV), "dof": torch.tensor(dof, device=DEV), "body": torch.zeros((R, B, 13), device=DEV),
+             "force": torch.zeros((R, B, 3), device=DEV), "torque": torch.zeros((R, D), device=DEV), "timestep": ts0.clone(),
+             "time": torch.zeros(R, device=DEV), "table": torch.tensor(rows.view(np.int32).reshape(R, 16), device=DEV)}
+        for v in t.values():
+            v[n:] = guard[v.dtype]
+        steps = []
+        for act in acts:
+            args = (_hip.stream(), _hip.c_vp(model.data_ptr()), ter, n, p(t["root"]), p(t["dof"]), p(t["body"]), p(t["force"]), p(offsets), p(act),
+                    p(lo), p(hi), 4, 1.0 / 120.0)
+            clock = (p(t["timestep"]), p(t["time"]), DT)
+            _hip.check(L.parc_sim_step_tick(*args, *clock) if entry == "tick" else
+                       L.parc_sim_step_ctl(*args, 2, sim_ctl.MODES["torque"], p(t["torque"]), *clock) if entry == "ctl" else
+                       L.parc_sim_step_phys(*args, 2, p(t["table"]), sim_ctl.MODES["pd"], None, *clock), entry)
+            torch.cuda.synchronize()
+            steps.append({k: v.clone() for k, v in t.items()})
+        return steps
+
+    for entry in ("tick", "ctl", "phys"):
+        tail, full = run(entry, LIVE), run(entry, R)
+        for k, (a, b) in enumerate(zip(tail, full), start=1):
+            for name in ["root", "dof", "body", "force"] + (["torque"] if entry == "ctl" else []):
+                assert torch.equal(a[name][:LIVE], b[name][:LIVE]) and torch.isfinite(a[name][:LIVE]).all(), (entry, k, name)
+            for out in (a, b):
+                assert torch.equal(out["timestep"][:LIVE], ts0[:LIVE] + k), (entry, k)
+                assert torch.equal(out["time"][:LIVE], out["timestep"][:LIVE].float() * torch.tensor(DT, device=DEV)), (entry, k)
+                assert entry != "phys" or (out["table"][:LIVE, left] == 2 - k).all(), (entry, k)
+            for name, v in a.items():
+                assert (v[LIVE:] == guard[v.dtype]).all(), (entry, k, name)
+        assert not torch.equal(tail[1]["dof"][:LIVE], tail[0]["dof"][:LIVE]), entry

@@ -16,13 +16,7 @@ void ctl_lane(int lane, const CtlArgs &c) {
 }
 void ctl_lane_body(int lane, void *p) {
     const CtlArgs &c = *(const CtlArgs *)p;
-    switch (c.mode) {
-    case PARC_SIM_CTL_PD: ctl_lane<PARC_SIM_CTL_PD>(lane, c); break;
-    case PARC_SIM_CTL_VEL: ctl_lane<PARC_SIM_CTL_VEL>(lane, c); break;
-    case PARC_SIM_CTL_TORQUE: ctl_lane<PARC_SIM_CTL_TORQUE>(lane, c); break;
-    case PARC_SIM_CTL_PD_EXP: ctl_lane<PARC_SIM_CTL_PD_EXP>(lane, c); break;
-    default: ctl_lane<PARC_SIM_CTL_PD_1D>(lane, c); break;
-    }
+    (void)parc_sim::ctl_dispatch(c.mode, [&](auto m) { ctl_lane<decltype(m)::value>(lane, c); });      // (the entry point has refused any other mode)
 }
 }  // namespace
 

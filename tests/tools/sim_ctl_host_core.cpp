@@ -4,17 +4,19 @@
 #include "../../oracle/sim_host.cpp"
 
 namespace {
-template <int MODE>
+// PHYS: with the table of per-env physics parameters (sim_phys_host_core.cpp), env e steps with its row
+template <int MODE, bool PHYS = false>
 void step_core(const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state, float *dof_state, float *rigid_body_state,
                float *contact_forces, const float *env_offsets, const float *action, const float *action_low, const float *action_high,
-               int n_substeps, float h, int hold, float *dof_torque) {
+               int n_substeps, float h, int hold, float *dof_torque, parc_sim_env_params_t *env_params = nullptr) {
     const int B = model->num_bodies, D = model->dof_size;
     for (int e = 0; e < n_envs; ++e) {
         parc_sim::Scratch s;
         if (g_fill >= 0) memset((void *)&s, g_fill, sizeof s);
-        parc_sim::env_step_ctl<MODE>(*model, terrain, env_offsets + 3 * (size_t)e, root_state + 13 * (size_t)e, dof_state + 2 * (size_t)D * e,
-                                     rigid_body_state + 13 * (size_t)B * e, contact_forces + 3 * (size_t)B * e, action + (size_t)D * e,
-                                     action_low, action_high, n_substeps, h, s, hold, dof_torque ? dof_torque + (size_t)D * e : nullptr);
+        parc_sim::env_step_ctl<MODE, PHYS>(*model, terrain, env_offsets + 3 * (size_t)e, root_state + 13 * (size_t)e,
+                                           dof_state + 2 * (size_t)D * e, rigid_body_state + 13 * (size_t)B * e,
+                                           contact_forces + 3 * (size_t)B * e, action + (size_t)D * e, action_low, action_high, n_substeps, h, s,
+                                           hold, dof_torque ? dof_torque + (size_t)D * e : nullptr, PHYS ? env_params + e : nullptr);
     }
 }
 }  // namespace
@@ -24,13 +26,8 @@ extern "C" int sim_ctl_host_step(const parc_sim_model_t *model, parc_terrain_t t
                                  const float *action_low, const float *action_high, int n_substeps, float h, int hold, int mode,
                                  float *dof_torque) {
     if (hold <= 0 || n_substeps % hold != 0) return PARC_EINVAL;
-    switch (mode) {
-    case PARC_SIM_CTL_PD: step_core<PARC_SIM_CTL_PD>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
-    case PARC_SIM_CTL_VEL: step_core<PARC_SIM_CTL_VEL>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
-    case PARC_SIM_CTL_TORQUE: step_core<PARC_SIM_CTL_TORQUE>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
-    case PARC_SIM_CTL_PD_EXP: step_core<PARC_SIM_CTL_PD_EXP>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
-    case PARC_SIM_CTL_PD_1D: step_core<PARC_SIM_CTL_PD_1D>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h, hold, dof_torque); break;
-    default: return PARC_EINVAL;
-    }
-    return 0;
+    return parc_sim::ctl_dispatch(mode, [&](auto m) {
+        step_core<decltype(m)::value>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action,
+                                      action_low, action_high, n_substeps, h, hold, dof_torque);
+    }) ? 0 : PARC_EINVAL;
 }

@@ -17,13 +17,7 @@ void phys_lane(int lane, const PhysArgs &p) {
 }
 void phys_lane_body(int lane, void *q) {
     const PhysArgs &p = *(const PhysArgs *)q;
-    switch (p.c.mode) {
-    case PARC_SIM_CTL_PD: phys_lane<PARC_SIM_CTL_PD>(lane, p); break;
-    case PARC_SIM_CTL_VEL: phys_lane<PARC_SIM_CTL_VEL>(lane, p); break;
-    case PARC_SIM_CTL_TORQUE: phys_lane<PARC_SIM_CTL_TORQUE>(lane, p); break;
-    case PARC_SIM_CTL_PD_EXP: phys_lane<PARC_SIM_CTL_PD_EXP>(lane, p); break;
-    default: phys_lane<PARC_SIM_CTL_PD_1D>(lane, p); break;
-    }
+    (void)parc_sim::ctl_dispatch(p.c.mode, [&](auto m) { phys_lane<decltype(m)::value>(lane, p); });      // (the entry point has refused any other mode)
 }
 }  // namespace
 

@@ -3,23 +3,6 @@
 // step without a table (sim_ctl_host_step) and the step with one (sim_phys_host_step), the two sides of the bit-equality checks.
 #include "sim_ctl_host_core.cpp"
 
-namespace {
-template <int MODE>
-void step_core_phys(const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state, float *dof_state,
-                    float *rigid_body_state, float *contact_forces, const float *env_offsets, const float *action, const float *action_low,
-                    const float *action_high, int n_substeps, float h, int hold, float *dof_torque, parc_sim_env_params_t *env_params) {
-    const int B = model->num_bodies, D = model->dof_size;
-    for (int e = 0; e < n_envs; ++e) {
-        parc_sim::Scratch s;
-        if (g_fill >= 0) memset((void *)&s, g_fill, sizeof s);
-        parc_sim::env_step_ctl<MODE, true>(*model, terrain, env_offsets + 3 * (size_t)e, root_state + 13 * (size_t)e,
-                                           dof_state + 2 * (size_t)D * e, rigid_body_state + 13 * (size_t)B * e,
-                                           contact_forces + 3 * (size_t)B * e, action + (size_t)D * e, action_low, action_high, n_substeps, h, s,
-                                           hold, dof_torque ? dof_torque + (size_t)D * e : nullptr, env_params + e);
-    }
-}
-}  // namespace
-
 // the argument rules of parc_sim_step_phys that concern the table (the host build sees the rows directly)
 extern "C" int sim_phys_host_check(const parc_sim_env_params_t *env_params, int n_envs) {
     if (!env_params || n_envs < 0) return PARC_EINVAL;
@@ -34,19 +17,8 @@ extern "C" int sim_phys_host_step(const parc_sim_model_t *model, parc_terrain_t 
                                   float *dof_torque, parc_sim_env_params_t *env_params) {
     if (hold <= 0 || n_substeps % hold != 0) return PARC_EINVAL;
     if (sim_phys_host_check(env_params, n_envs) != PARC_OK) return PARC_EINVAL;
-#define PHYS_CASE(M)                                                                                                                      \
-    case M:                                                                                                                               \
-        step_core_phys<M>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, \
-                          action_high, n_substeps, h, hold, dof_torque, env_params);                                                      \
-        break;
-    switch (mode) {
-        PHYS_CASE(PARC_SIM_CTL_PD)
-        PHYS_CASE(PARC_SIM_CTL_VEL)
-        PHYS_CASE(PARC_SIM_CTL_TORQUE)
-        PHYS_CASE(PARC_SIM_CTL_PD_EXP)
-        PHYS_CASE(PARC_SIM_CTL_PD_1D)
-    default: return PARC_EINVAL;
-    }
-#undef PHYS_CASE
-    return 0;
+    return parc_sim::ctl_dispatch(mode, [&](auto m) {
+        step_core<decltype(m)::value, true>(model, terrain, n_envs, root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action,
+                                            action_low, action_high, n_substeps, h, hold, dof_torque, env_params);
+    }) ? 0 : PARC_EINVAL;
 }
