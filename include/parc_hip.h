@@ -373,6 +373,18 @@ int64_t parc_sgd_workspace_floats(void);
 int parc_sgd_momentum_step(void *stream, int64_t n, float *params, const float *grad, float *momentum_buf, float max_norm, float lr,
                            float momentum, float weight_decay, float *workspace, float *norm_out);
 
+/* The same two passes for optimizer type "Adam" (MPOptimizer -> torch.optim.AdamW, learning/mp_optimizer.py:51-62; amsgrad and
+ * maximize off), torch's single-tensor order: coef as above, g' = coef grad, params *= 1 - lr weight_decay,
+ * exp_avg = beta1 exp_avg + (1 - beta1) g', exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g'^2,
+ * params -= (lr / (1 - beta1^step)) exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^step) + eps).  step counts from 1; zero moment buffers
+ * and step 1 are torch's first step.  The bias corrections are taken on the host in double; every float setting is read as the
+ * double its shortest decimal form names (0.999f is 0.999).  grad is left as it was and must be 16-byte aligned; params, exp_avg and
+ * exp_avg_sq may be misaligned (an element-wise path with the same arithmetic).  workspace: parc_sgd_workspace_floats() floats;
+ * norm_out (may be NULL): the gradient norm, written when max_norm > 0.  PARC_EINVAL: a NULL pointer other than norm_out, n < 0,
+ * step < 1, a misaligned grad, a beta outside [0, 1), eps <= 0 - before any launch. */
+int parc_adamw_step(void *stream, int64_t n, float *params, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t step,
+                    float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, float *workspace, float *norm_out);
+
 /* ---- K12: Normalizer.normalize  learning/normalizer.py:60-63 in one pass: out = clamp((x - mean) / std, -clip, clip).
  * x, out [rows, dim] row-major, mean / std [dim]; dim a multiple of 4, 16-byte aligned pointers; out may alias x. */
 int parc_normalize_clamp(void *stream, int64_t rows, int dim, const float *x, const float *mean, const float *stdv, float clip, float *out);

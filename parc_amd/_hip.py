@@ -243,6 +243,8 @@ def _declare(L):
     L.parc_sgd_workspace_floats.restype = c_i64
     L.parc_sgd_momentum_step.argtypes = [c_vp, c_i64, c_vp, c_vp, c_vp, c_f, c_f, c_f, c_f, c_vp, c_vp]
     L.parc_sgd_momentum_step.restype = c_int
+    L.parc_adamw_step.argtypes = [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp]
+    L.parc_adamw_step.restype = c_int
     L.parc_return_tracker_update.argtypes = [c_vp, c_int, c_int, c_vp, c_i64] + [c_vp] * 8
     L.parc_return_tracker_workspace_floats.argtypes = [c_int]
     L.parc_return_tracker_workspace_floats.restype = c_i64
@@ -273,7 +275,7 @@ EXPORTED = ["parc_abi_version", "parc_refresh_ray_obs_hfs", "parc_refresh_obs_hf
             "parc_forward_kinematics", "parc_calc_motion_frame", "parc_motion_lib_build", "parc_track_post_step",
             "parc_update_fail_rates", "parc_td_lambda_return", "parc_adv_normalize", "parc_reset_apply", "parc_ppo_loss", "parc_ppo_workspace_floats", "parc_record_step", "parc_return_tracker_update", "parc_normalize_clamp",
             "parc_action_head", "parc_points_hf_sdf", "parc_moments_workspace_floats", "parc_moments_accumulate", "parc_reset_sample_apply", "parc_return_tracker_workspace_floats", "parc_scale_by_clipped_norm", "parc_relu_bwd_workspace_floats",
-            "parc_relu_bwd_bias_grad", "parc_ppo_loss_packed", "parc_weighted_colsum", "parc_sgd_workspace_floats", "parc_sgd_momentum_step",
+            "parc_relu_bwd_bias_grad", "parc_ppo_loss_packed", "parc_weighted_colsum", "parc_sgd_workspace_floats", "parc_sgd_momentum_step", "parc_adamw_step",
             "parc_pose_chain_forward", "parc_pose_chain_backward", "parc_points_hf_sdf_grad", "parc_body_points_world", "parc_body_points_world_grad",
             "parc_quat_diff_angle", "parc_quat_diff_angle_grad", "parc_temporal_terms", "parc_temporal_terms_grad", "parc_step_tail",
             "parc_assemble_obs", "parc_track_post_step_timed", "parc_rng_step", "parc_obs_ingest", "parc_action_head_record",

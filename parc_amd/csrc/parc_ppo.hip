@@ -3,7 +3,10 @@
 // Gaussian policy with state-independent log-std: the ~120 small elementwise / reduction launches of the autograd
 // graph between the two MLP outputs and the scalar loss become three launches with a deterministic reduction order.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/parc_hip.h"
 
@@ -599,6 +602,113 @@ extern "C" int parc_sgd_momentum_step(void *stream, int64_t n, float *params, co
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(sgd_momentum_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (size_t)n, params, grad, momentum_buf, workspace, max_norm,
                        lr, momentum, weight_decay, norm_out);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? PARC_OK : (int)e;
+}
+
+// =============================================================================================
+// The same two passes for `optimizer.type: Adam` (MPOptimizer -> torch.optim.AdamW, learning/mp_optimizer.py:51-62): pass 1 is
+// sumsq_partial_kernel above, pass 2 folds the partials like the SGD step and then runs torch's single-tensor AdamW on its elements,
+// operation for operation and in torch's order (each line below is one rounded fp32 operation of _single_tensor_adamw; contraction is
+// off so that the compiler fuses nothing else):
+//   g' = coef g;  p *= 1 - lr wd;  m = fma(1 - b1, g' - m, m) [lerp_];  v = fma((1 - b2) g', g', b2 v) [mul_, addcmul_];
+//   p += ((-lr / (1 - b1^t)) m) / (sqrt(v) / sqrt(1 - b2^t) + eps) [addcdiv_]
+// 28 B per element of plain 16-byte loads and stores, no cache-policy bits: the parameters are read again by the next minibatch's
+// GEMMs and all four buffers (170 MB at the model's size) by the next step, which the 256 MB last-level cache can serve; a
+// non-temporal variant was not measured.  One resident round of workgroups (8 x 256 threads per CU), grid-stride.
+// =============================================================================================
+struct adamw_consts_t {
+    float decay, w1, beta2, w2, neg_step, bc2_sqrt, eps;
+};
+
+__device__ __forceinline__ void adamw_element(float &p, float g, float &m, float &v, float coef, const adamw_consts_t &c) {
+#pragma clang fp contract(off)
+    g = coef * g;
+    const float pd = p * c.decay;
+    m = fmaf(c.w1, g - m, m);
+    v = fmaf(c.w2 * g, g, v * c.beta2);
+    const float den = sqrtf(v) / c.bc2_sqrt + c.eps;
+    p = pd + (c.neg_step * m) / den;
+}
+
+__global__ __launch_bounds__(256) void adamw_clip_kernel(size_t n, size_t n4, float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                         float *__restrict__ v, const float *__restrict__ partial, float max_norm, adamw_consts_t c,
+                                                         float *norm_out) {
+    __shared__ float s_red[256];
+    float coef = 1.0f;
+    if (max_norm > 0.f) {
+        float a = 0.f;
+#pragma unroll
+        for (int k = 0; k < SGD_PARTS / 256; ++k) a += partial[threadIdx.x * (SGD_PARTS / 256) + k];      // as sgd_momentum_clip_kernel
+        s_red[threadIdx.x] = a;
+        __syncthreads();
+        for (int w = 128; w >= 1; w >>= 1) {
+            if ((int)threadIdx.x < w) s_red[threadIdx.x] += s_red[threadIdx.x + w];
+            __syncthreads();
+        }
+        const float norm = sqrtf(s_red[0]);
+        coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+        if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+    }
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    float4 *p4 = (float4 *)p, *m4 = (float4 *)m, *v4 = (float4 *)v;       // n4 > 0 only when all four buffers are 16-byte aligned
+    const float4 *g4 = (const float4 *)g;
+    for (size_t i = tid; i < n4; i += stride) {
+        float4 pi = p4[i], mi = m4[i], vi = v4[i];
+        const float4 gi = g4[i];
+        adamw_element(pi.x, gi.x, mi.x, vi.x, coef, c);
+        adamw_element(pi.y, gi.y, mi.y, vi.y, coef, c);
+        adamw_element(pi.z, gi.z, mi.z, vi.z, coef, c);
+        adamw_element(pi.w, gi.w, mi.w, vi.w, coef, c);
+        p4[i] = pi; m4[i] = mi; v4[i] = vi;
+    }
+    for (size_t i = 4 * n4 + tid; i < n; i += stride) {       // the tail of the vector path, or every element when a buffer is misaligned
+        float pi = p[i], mi = m[i], vi = v[i];
+        adamw_element(pi, g[i], mi, vi, coef, c);
+        p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+}
+
+// A float hyper-parameter as the double its shortest decimal form names (0.999f -> 0.999, not 0.99900001287...): the settings are
+// decimal literals that torch keeps as Python doubles, and 1 - beta2 taken from the widened float would be off by 1.3e-5 relative.
+static double decimal_double(float x) {
+    char buf[32];
+    for (int digits = 1; digits <= 9; ++digits) {
+        snprintf(buf, sizeof buf, "%.*g", digits, (double)x);
+        if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
+    }
+    return (double)x;
+}
+
+#define ADAMW_MAX_BLOCKS 2048
+extern "C" int parc_adamw_step(void *stream, int64_t n, float *params, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t step,
+                               float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, float *workspace, float *norm_out) {
+    if (n < 0 || step < 1 || !params || !grad || !exp_avg || !exp_avg_sq || !workspace || ((uintptr_t)grad & 15)) return PARC_EINVAL;
+    if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f)) return PARC_EINVAL;
+    if (n == 0) return PARC_OK;
+    static thread_local float key[5] = {-1.f, -1.f, -1.f, -1.f, -1.f};      // the settings do not change between steps: convert them once
+    static thread_local double val[5];
+    const float in[5] = {lr, beta1, beta2, eps, weight_decay};
+    for (int k = 0; k < 5; ++k)
+        if (!(in[k] == key[k])) { val[k] = decimal_double(in[k]); key[k] = in[k]; }
+    const double lr_d = val[0], b1 = val[1], b2 = val[2];
+    adamw_consts_t c;
+    c.decay = (float)(1.0 - lr_d * val[4]);
+    c.w1 = (float)(1.0 - b1);
+    c.beta2 = (float)b2;
+    c.w2 = (float)(1.0 - b2);
+    c.neg_step = (float)(-(lr_d / (1.0 - pow(b1, (double)step))));
+    c.bc2_sqrt = (float)sqrt(1.0 - pow(b2, (double)step));
+    c.eps = (float)val[3];
+    hipStream_t st = (hipStream_t)stream;
+    if (max_norm > 0.f)
+        hipLaunchKernelGGL(sumsq_partial_kernel, dim3(SGD_PARTS), dim3(256), 0, st, (size_t)n / 4, (const float4 *)grad, (size_t)n, grad, workspace);
+    const bool vec = !(((uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15);
+    const size_t n4 = vec ? (size_t)n / 4 : 0, work = vec ? n4 + 3 : (size_t)n;
+    size_t blocks = (work + 255) / 256;
+    if (blocks > ADAMW_MAX_BLOCKS) blocks = ADAMW_MAX_BLOCKS;
+    hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (size_t)n, n4, params, grad, exp_avg, exp_avg_sq, workspace, max_norm,
+                       c, norm_out);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? PARC_OK : (int)e;
 }

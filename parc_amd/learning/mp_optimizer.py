@@ -24,9 +24,11 @@ class MPOptimizer:
         wd = float(config.get("weight_decay", 0.0))
         # one multi-tensor launch per step where torch offers it (device parameters): same update rule, 1 kernel instead of 3
         fused = {"fused": True} if (param_list[0].is_cuda and config.get("fused_optimizer", True)) else {}
-        will_be_flat = (config["type"] == "SGD" and param_list[0].is_cuda and param_list[0].dtype == torch.float32 and bool(config.get("flat_sgd", True)))
+        on_device_fp32 = param_list[0].is_cuda and param_list[0].dtype == torch.float32
+        will_be_flat = on_device_fp32 and ((config["type"] == "SGD" and bool(config.get("flat_sgd", True))) or
+                                           (config["type"] == "Adam" and bool(config.get("flat_adam", True))))
         if will_be_flat:
-            self._optimizer = None            # the flat SGD step below replaces it: no torch optimizer object that is never stepped
+            self._optimizer = None            # the flat step below replaces it: no torch optimizer object that is never stepped
         elif config["type"] == "SGD":
             self._optimizer = torch.optim.SGD(param_list, lr, momentum=0.9, weight_decay=wd, **fused)
         elif config["type"] == "Adam":
@@ -41,9 +43,11 @@ class MPOptimizer:
             off += p.numel()
         # SGD on the GPU: parameters and momentum live in flat buffers too (every parameter is a view, like its gradient), and clip +
         # momentum + update are two passes over them (parc_sgd_momentum_step) instead of norm, scale, multi-tensor SGD and a fill
-        self._flat_sgd = (config["type"] == "SGD" and param_list[0].is_cuda and param_list[0].dtype == torch.float32
-                          and bool(config.get("flat_sgd", True)))
-        if self._flat_sgd:
+        self._flat_sgd = config["type"] == "SGD" and will_be_flat
+        # Adam on the GPU: the same layout with two moment buffers, and clip + AdamW are the same two passes (parc_adamw_step)
+        self._flat_adam = config["type"] == "Adam" and will_be_flat
+        self._flat = self._flat_sgd or self._flat_adam
+        if self._flat:
             from .. import _hip
             self._flat_param = torch.empty(n, dtype=torch.float32, device=param_list[0].device)
             off = 0
@@ -53,7 +57,13 @@ class MPOptimizer:
                     view.copy_(p)
                     p.data = view
                     off += p.numel()
-            self._flat_mom = torch.zeros_like(self._flat_param)
+            if self._flat_sgd:
+                self._flat_mom = torch.zeros_like(self._flat_param)
+            else:
+                self._flat_exp_avg = torch.zeros_like(self._flat_param)
+                self._flat_exp_avg_sq = torch.zeros_like(self._flat_param)
+                self._adam_steps = 0                    # AdamW's own step count (the bias correction): reset_state() restarts it
+                self._betas, self._eps = (0.9, 0.999), 1e-8         # torch.optim.AdamW's defaults, as the reference leaves them
             self._sgd_ws = torch.empty(int(_hip.lib().parc_sgd_workspace_floats()), dtype=torch.float32, device=self._flat_param.device)
             self._grad_norm = torch.zeros(1, dtype=torch.float32, device=self._flat_param.device)
             self._lr, self._momentum, self._wd = lr, 0.9, wd
@@ -173,6 +183,10 @@ class MPOptimizer:
         """Forget the optimizer's moments (tests restart from saved weights)."""
         if self._flat_sgd:
             self._flat_mom.zero_()
+        elif self._flat_adam:
+            self._flat_exp_avg.zero_()
+            self._flat_exp_avg_sq.zero_()
+            self._adam_steps = 0
         else:
             self._optimizer.state.clear()
 
@@ -180,13 +194,13 @@ class MPOptimizer:
 
     def _check_aliasing(self):
         """Every parameter and its gradient must still BE the slice of the flat buffers they were bound to at construction: the flat
-        SGD step (and the in-place gradient exchange) update the flat buffers only, so anything that rebinds `p.data` / `p.grad`
+        SGD / AdamW step (and the in-place gradient exchange) update the flat buffers only, so anything that rebinds `p.data` / `p.grad`
         afterwards - load_state_dict(assign=True), module.to() / .float() onto another device or dtype, zero_grad(set_to_none=True) -
         would leave the model reading tensors that training no longer updates, silently.  Pointer compares only: no device work."""
         off = 0
         for p in self._param_list:
             nb = p.element_size()
-            if self._flat_sgd and p.data_ptr() != self._flat_param.data_ptr() + off * nb:
+            if self._flat and p.data_ptr() != self._flat_param.data_ptr() + off * nb:
                 raise RuntimeError("a parameter of shape {} no longer aliases the optimizer's flat parameter buffer (something rebound "
                                    "p.data after the optimizer was built): rebuild the MPOptimizer".format(tuple(p.shape)))
             if p.grad is None or p.grad.data_ptr() != self._flat_grad.data_ptr() + off * nb:
@@ -203,6 +217,18 @@ class MPOptimizer:
             _hip.check(_hip.lib().parc_sgd_momentum_step(_hip.stream(), self._flat_param.numel(), _hip.ptr(self._flat_param), _hip.ptr(self._flat_grad),
                                                          _hip.ptr(self._flat_mom), max_norm, float(self._lr), float(self._momentum), float(self._wd),
                                                          _hip.ptr(self._sgd_ws), _hip.ptr(self._grad_norm)), "parc_sgd_momentum_step")
+            if mp_util.enable_mp() and self._cadence == "minibatch" and self._steps % self.CHECK_SYNC_STEPS == 0:
+                assert self._check_synced(), "Network parameters desynchronized"
+            self._steps += 1
+            return
+        if self._flat_adam:
+            from .. import _hip
+            max_norm = float(kwargs["max_norm"]) if "model" in kwargs else -1.0
+            self._adam_steps += 1
+            _hip.check(_hip.lib().parc_adamw_step(_hip.stream(), self._flat_param.numel(), _hip.ptr(self._flat_param), _hip.ptr(self._flat_grad),
+                                                  _hip.ptr(self._flat_exp_avg), _hip.ptr(self._flat_exp_avg_sq), self._adam_steps, max_norm,
+                                                  float(self._lr), float(self._betas[0]), float(self._betas[1]), float(self._eps), float(self._wd),
+                                                  _hip.ptr(self._sgd_ws), _hip.ptr(self._grad_norm)), "parc_adamw_step")
             if mp_util.enable_mp() and self._cadence == "minibatch" and self._steps % self.CHECK_SYNC_STEPS == 0:
                 assert self._check_synced(), "Network parameters desynchronized"
             self._steps += 1
@@ -227,9 +253,9 @@ class MPOptimizer:
         all-reduce of a flat buffer (no-op for the per-minibatch cadence or a single process)."""
         if not (mp_util.enable_mp() and self._cadence == "epoch"):
             return
-        if self._flat_sgd:
+        if self._flat:
             with torch.no_grad():
-                for flat in (self._flat_param, self._flat_mom):
+                for flat in self._epoch_exchange_buffers():
                     torch.distributed.all_reduce(flat, op=torch.distributed.ReduceOp.SUM)
                     flat /= mp_util.get_num_procs()
             return
@@ -246,13 +272,20 @@ class MPOptimizer:
                 t.copy_(flat[off:off + t.numel()].view_as(t))
                 off += t.numel()
 
+    def _epoch_exchange_buffers(self):
+        """The flat buffers end_epoch() averages over the ranks, in place: the parameters and the optimizer's moments."""
+        assert self._flat
+        if self._flat_sgd:
+            return [self._flat_param, self._flat_mom]
+        return [self._flat_param, self._flat_exp_avg, self._flat_exp_avg_sq]
+
     def get_steps(self):
         return self._steps
 
     def _flat_view_of_params(self):
         """(flat tensor holding every parameter, scatter-back function or None): the flat parameter buffer itself where the parameters
-        are views of it (flat SGD), a packed copy otherwise"""
-        if self._flat_sgd:
+        are views of it (flat SGD / AdamW), a packed copy otherwise"""
+        if self._flat:
             return self._flat_param, None
         flat = torch.cat([p.detach().reshape(-1) for p in self._param_list])
 
