@@ -1861,27 +1861,41 @@ __global__ __launch_bounds__(256) void reset_cdf_kernel(int M, const float *__re
 
 #define RESET_CDF_LDS 4096          // clips whose cumulative weights a workgroup builds for itself in LDS (16 KB); more: reset_cdf_kernel first
 
-// cumulative weights into `out` (LDS or global), by the 256 threads of one workgroup: thread t sums its chunk, the chunk sums are
-// scanned, every thread writes its chunk's running sums - the same steps, hence the same fp32 sums, in every workgroup that runs it
+// fp32 product a clip is drawn in proportion to; __fmul_rn so that it never contracts into the addition that follows it
+PARC_DEV float reset_clip_product(const float *__restrict__ weights, const float *__restrict__ fail_rates, float min_w, int i) {
+    return __fmul_rn(fail_rates ? fmaxf(fail_rates[i], min_w) : 1.0f, weights[i]);
+}
+
+// cumulative weights into `out` (LDS or global), by the 256 threads of one workgroup - the same steps, hence the same fp32 sums, in
+// every workgroup that runs it.  table[i] = base[t] + (running sum inside chunk t), and base[t + 1] IS the last entry of chunk t:
+// base[t + 1] = base[t] + (sum of chunk t), the chunk sum being the same chain of additions as the chunk's last running sum.  Rounding
+// is monotonic, so the table never decreases and stays flat across clips whose product is 0, inside a chunk and over its seams, which
+// the bisection below and "a clip of weight 0 is never drawn" rely on.  (Chunk bases from a parallel scan are another rounding of the
+// same sums than the running sums next to them: that table stepped down at seams and up on weight-0 clips, DESIGN.md.)  The bases are a
+// serial chain over the chunks, by one thread: at most 256 dependent additions.
 PARC_DEV void build_reset_cdf(int M, const float *__restrict__ weights, const float *__restrict__ fail_rates, float min_w, float *out, float *part) {
     const int chunk = (M + 255) / 256;
+    const int nchunks = (M + chunk - 1) / chunk;
     const int i0 = min((int)threadIdx.x * chunk, M), i1 = min(i0 + chunk, M);
     float s = 0.f;
-    for (int i = i0; i < i1; ++i) s += (fail_rates ? fmaxf(fail_rates[i], min_w) : 1.0f) * weights[i];
+    for (int i = i0; i < i1; ++i) s = __fadd_rn(s, reset_clip_product(weights, fail_rates, min_w, i));
     part[threadIdx.x] = s;
     __syncthreads();
-    // inclusive scan of the 256 chunk sums by all threads (log steps; one thread walking them cost as much as the launch this saves)
-    for (int off = 1; off < 256; off <<= 1) {
-        float v = part[threadIdx.x];
-        if ((int)threadIdx.x >= off) v += part[threadIdx.x - off];
-        __syncthreads();
-        part[threadIdx.x] = v;
-        __syncthreads();
+    if (threadIdx.x == 0) {
+        float base = 0.f;
+#pragma unroll 8
+        for (int t = 0; t < nchunks; ++t) {
+            const float v = part[t];
+            part[t] = base;
+            base = __fadd_rn(base, v);
+        }
     }
-    float run = part[threadIdx.x] - s;           // sum of the chunks in front of this thread's
+    __syncthreads();
+    const float base = part[threadIdx.x];
+    float run = 0.f;
     for (int i = i0; i < i1; ++i) {
-        run += (fail_rates ? fmaxf(fail_rates[i], min_w) : 1.0f) * weights[i];
-        out[i] = run;
+        run = __fadd_rn(run, reset_clip_product(weights, fail_rates, min_w, i));
+        out[i] = __fadd_rn(base, run);
     }
     __syncthreads();
 }
