@@ -30,10 +30,11 @@ _ALIASES = {
     "learning.tracking_error_tracker": "learning.tracking_error_tracker",
     "PARC.util.create_dataset": "util.create_dataset",
     "tools.motion_opt.motion_optimization": "tools.motion_opt.motion_optimization",
+    "tools.procgen.mdm_path": "tools.procgen.mdm_path", "tools.motion_tests.compute_losses": "tools.motion_tests.compute_losses",
     "zmotion_editing_tools": "zmotion_editing_tools", "zmotion_editing_tools.motion_edit_lib": "zmotion_editing_tools.motion_edit_lib",
 }
 # pure namespace packages of the reference that hold nothing this path needs besides the sub-module above
-_NAMESPACES = ("PARC", "PARC.util", "tools", "tools.motion_opt")
+_NAMESPACES = ("PARC", "PARC.util", "tools", "tools.motion_opt", "tools.procgen", "tools.motion_tests")
 
 
 def install_reference_aliases(strict=True):

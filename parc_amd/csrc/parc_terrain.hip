@@ -11,24 +11,12 @@
 #include <stdint.h>
 
 #include "../../include/parc_hip.h"
+#include "parc_sdf_core.h"      // column_sd, hf_window_min
 
 #define SDF_THREADS 64
 
-// sdBox of one column: q = |p - centre| - half extents; |max(q, 0)| + min(max(q.x, q.y, q.z), 0), same fp32 operations as the
-// reference (:1862-1871)
-__device__ __forceinline__ float column_sd(float px, float py, float pz, float cx, float cy, float h, float half_x, float half_y, float base_z,
-                                           float top_z, int inverted) {
-    const float cz = inverted ? (h + top_z) / 2.0f : (h + base_z) / 2.0f;
-    const float hz = inverted ? (top_z - h) / 2.0f : (h - base_z) / 2.0f;
-    const float qx = fabsf(px - cx) - half_x, qy = fabsf(py - cy) - half_y, qz = fabsf(pz - cz) - hz;
-    const float ax = fmaxf(qx, 0.f), ay = fmaxf(qy, 0.f), az = fmaxf(qz, 0.f);
-    return __fsqrt_rn(ax * ax + ay * ay + az * az) + fminf(fmaxf(qx, fmaxf(qy, qz)), 0.f);
-}
-
-// One thread per point.  The minimum over ALL columns is found exactly without visiting all of them: the distance d0 to the column under
-// the point bounds the answer, and a column more than R = floor(d0 / cell) + 2 cells away in x or in y is further than d0 in that
-// coordinate alone (columns do not overlap in xy), so only the (2R+1)^2 window is scanned - in the same cell order as a full scan, so
-// "first column that attains the minimum" is the same column.  Heights come straight from L2 (a heightfield is a few hundred KB).
+// One thread per point.  The minimum over ALL columns is found exactly without visiting all of them: hf_window_min (parc_sdf_core.h) scans
+// only the window of columns that can hold it.  Heights come straight from L2 (a heightfield is a few hundred KB).
 __global__ __launch_bounds__(SDF_THREADS) void points_hf_sdf_kernel(int n_points, int dim_x, int dim_y, const float *__restrict__ points,
                                                                     const float *__restrict__ hf, const float *__restrict__ min_box_center,
                                                                     const float *__restrict__ x_points, const float *__restrict__ y_points,
@@ -41,34 +29,8 @@ __global__ __launch_bounds__(SDF_THREADS) void points_hf_sdf_kernel(int n_points
     const float px = pt[0], py = pt[1], pz = pt[2];
     const float *hfb = hf + (size_t)bi * dim_x * dim_y;
     const float ox = min_box_center[2 * bi], oy = min_box_center[2 * bi + 1];
-    const float top_z = -base_z;
-    const float cell_x = 2.0f * half_x, cell_y = 2.0f * half_y;
-    // NaN / inf coordinates: the comparisons below are all false for NaN, so the window degenerates to the whole field
-    const float fi = rintf((px - ox) / cell_x), fj = rintf((py - oy) / cell_y);
-    const int i0 = (int)fminf(fmaxf(fi, 0.f), (float)(dim_x - 1)), j0 = (int)fminf(fmaxf(fj, 0.f), (float)(dim_y - 1));
-    const float d0 = column_sd(px, py, pz, x_points[i0] + ox, y_points[j0] + oy, hfb[i0 * dim_y + j0], half_x, half_y, base_z, top_z, inverted);
-    int i_lo = 0, i_hi = dim_x - 1, j_lo = 0, j_hi = dim_y - 1;
-    if (d0 < 3.0e8f) {              // also false for NaN
-        const float bound = fmaxf(d0, 0.f);
-        const int rx = (int)(bound / cell_x) + 2, ry = (int)(bound / cell_y) + 2;
-        i_lo = max(i0 - rx, 0);
-        i_hi = min(i0 + rx, dim_x - 1);
-        j_lo = max(j0 - ry, 0);
-        j_hi = min(j0 + ry, dim_y - 1);
-    }
-    float best = INFINITY;
-    int best_cell = 0;
-    for (int i = i_lo; i <= i_hi; ++i) {
-        const float cx = x_points[i] + ox;
-        const float *row = hfb + (size_t)i * dim_y;
-        for (int j = j_lo; j <= j_hi; ++j) {
-            const float sd = column_sd(px, py, pz, cx, y_points[j] + oy, row[j], half_x, half_y, base_z, top_z, inverted);
-            if (sd < best) {             // first column that attains the minimum
-                best = sd;
-                best_cell = i * dim_y + j;
-            }
-        }
-    }
+    int best_cell;
+    float best = hf_window_min(px, py, pz, hfb, dim_x, dim_y, ox, oy, x_points, y_points, half_x, half_y, base_z, inverted, best_cell);
     if (!(px == px && py == py && pz == pz)) best = __builtin_nanf("");   // a NaN coordinate: torch's abs / clamp / min propagate it, fmaxf / fminf above do not
     if (radius > 0.f) best -= radius;           // sdRoundBox: x - r is monotone, so it commutes with the min
     if (inverted) best = -best;
