@@ -21,7 +21,7 @@ from ..envs import base_env
 from ..gym_spaces import Box
 from ..util import mp_util
 from ..util.logger import Logger
-from . import dm_ppo_model, experience_buffer, mp_optimizer, normalizer, rl_util
+from . import dm_ppo_model, experience_buffer, mp_optimizer, normalizer, rl_util, unit_stats
 from .dm_ppo_return_tracker import DMPPOReturnTracker
 from .tracking_error_tracker import TrackingErrorTracker
 
@@ -91,6 +91,8 @@ class DMPPOAgent(torch.nn.Module):
         self._compute_times = []                         # (row, seconds) of the steps of this rollout, written in one go at its end
         self._replan_time_rows, self._replan_time_src = None, None
         self._ones_mask = None
+        self._unit_stats = None                          # learning/unit_stats.UnitStats while test_model2 / log_unit_stats collect
+        self._unit_report = None
         if getattr(self._env, "_report_tracking_error", False):
             self._test_tracking_error_tracker = TrackingErrorTracker(self.get_num_envs(), self._device)
 
@@ -125,6 +127,7 @@ class DMPPOAgent(torch.nn.Module):
         self._clip_grad_norm = config.get("clip_grad_norm", False)
         self._max_grad_norm = config.get("max_grad_norm", 0.5)
         self._critic_loss_type = config.get("critic_loss_type", "L2")
+        self._log_unit_stats = bool(config.get("log_unit_stats", False))
 
     def _build_normalizers(self):
         """Observation normaliser that leaves the contact / heightmap segments untouched (dm_ppo_agent.py:78-117),
@@ -234,7 +237,7 @@ class DMPPOAgent(torch.nn.Module):
             self._obs_ingested = True
         else:
             norm_obs = self._obs_norm.normalize(obs)
-        dist = self._model.eval_actor(norm_obs)
+        dist = self._model.eval_actor(norm_obs) if self._unit_stats is None else self._eval_actor_with_unit_stats(norm_obs)
         if obs.is_cuda and dist.logstd.dim() == 2 and dist.logstd.stride(0) == 0 and self._config.get("fused_action_head", True):
             return self._decide_action_fused(dist, obs.shape[0])
         if self._mode == AgentMode.TRAIN:
@@ -296,6 +299,55 @@ class DMPPOAgent(torch.nn.Module):
         _hip.check(_hip.lib().parc_action_head(_hip.stream(), n, A, p(mean), p(dist.logstd[0].contiguous()), p(noise), p(mask),
                                                p(self._a_norm.get_mean()), p(self._a_norm.get_std()), p(a), p(logp)), "parc_action_head")
         return a, {"a_logp": logp, "rand_action_mask": mask}
+
+    # ------------------------------------------------------------------ unit statistics (dm_ppo_agent.py:607-773)
+    def _eval_actor_with_unit_stats(self, norm_obs):
+        """The actor forward of a step while the statistics are on: it runs once, and the update reads its hidden activations."""
+        st = self._unit_stats
+        dist, acts = self._model.eval_actor_tapped(norm_obs)
+        st.update(acts, dist.mean)
+        if st.print_every and st.steps % st.print_every == 0:
+            Logger.print("\n".join(unit_stats.report_lines(st.report())))
+        return dist
+
+    def _unit_stats_on(self, print_every=0):
+        """Allocate the statistics state, all running values at zero; raises for a network the device update does not cover."""
+        self._unit_stats = unit_stats.UnitStats(self._model, self.get_num_envs(), self._device, tap=getattr(self, "_unit_stats_tap", None))
+        self._unit_stats.print_every = int(print_every)
+
+    def _unit_stats_off(self, ranks=None):
+        """Keep the report (unit_report) and free the state."""
+        st, self._unit_stats = self._unit_stats, None
+        if st is not None:
+            self._unit_report = dict(st.report())
+            if ranks is not None:
+                self._unit_report = {"ranks": ranks, **self._unit_report}
+
+    def unit_report(self):
+        """The last statistics run as nested dicts of Python floats and ints: "ranks" (test_model2 only: per hidden layer and for the
+        mean net max_rank, stable_rank, avg_weight_mag), "layers" (per hidden layer num_dormant, num_units, percent_dormant and the
+        mean / std / max / min of activation and of utility), "mean_net" (see UnitStats.report for its two dormant figures) and
+        "steps".  None before the first run.  The statistics are this rank's own, as in the reference."""
+        return self._unit_report
+
+    def test_model2(self, num_episodes, verbose=False, k=100):
+        """test_model plus the reference's network-health figures (dm_ppo_agent.py:607-773): returns test_model's dict and leaves the
+        figures in unit_report().  The root process prints them once at the end in the reference's wording (the reference prints them
+        at every step); verbose=True also prints them every k steps, at the cost of one host read each."""
+        unit_stats.check_model(self._model)
+        self.eval()
+        self.set_mode(AgentMode.TEST)
+        ranks = unit_stats.model_rank_figures(self._model)
+        Logger.print("\n".join(unit_stats.rank_lines(ranks)))
+        self._curr_obs, self._curr_info = self._env.reset()
+        self._unit_stats_on(print_every=k if verbose else 0)
+        try:
+            info = self._rollout_test(int(np.ceil(num_episodes / mp_util.get_num_procs())))
+            self._unit_stats_off(ranks)
+        finally:
+            self._unit_stats = None                      # (a rollout that raised leaves no report, and no state behind)
+        Logger.print("\n".join(unit_stats.report_lines(self._unit_report)))
+        return info
 
     def step(self):
         action, action_info = self._decide_action(self._curr_obs, self._curr_info)
@@ -789,6 +841,12 @@ class DMPPOAgent(torch.nn.Module):
         L.log("Exp_Prob", self._get_exp_prob())
         if self._is_terrain_runner:
             L.log("replan timer", self._env.get_replan_time_buf().item())
+        if self._log_unit_stats and self._unit_report is not None:
+            for l, y in enumerate(self._unit_report["layers"]):
+                L.log("Dormant_Pct_L{}".format(l), y["percent_dormant"], collection="3_Units", quiet=True)
+                L.log("Act_Mean_L{}".format(l), y["activation"]["mean"], collection="3_Units", quiet=True)
+                L.log("Util_Mean_L{}".format(l), y["utility"]["mean"], collection="3_Units", quiet=True)
+            L.log("Dormant_Pct_MeanNet", self._unit_report["mean_net"]["percent_dormant"], collection="3_Units", quiet=True)
 
     def _output_train_model(self, it, out_model_file, int_output_dir):
         self.save(out_model_file)
@@ -808,7 +866,13 @@ class DMPPOAgent(torch.nn.Module):
             train_info = self._train_iter()
             output_iter = (self._iter % self._iters_per_output == 0)
             if output_iter:
-                test_info = self.test_model(self._test_episodes)
+                if self._log_unit_stats:
+                    self._unit_stats_on()                # started fresh at every periodic test rollout
+                try:
+                    test_info = self.test_model(self._test_episodes)
+                    self._unit_stats_off()
+                finally:
+                    self._unit_stats = None
                 extra = self._env.get_extra_log_info()
                 for coll in extra:
                     for k, v in extra[coll].items():

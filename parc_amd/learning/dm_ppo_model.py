@@ -161,6 +161,16 @@ class DMPPOModel(torch.nn.Module):
     def eval_actor(self, obs):
         return self._action_dist(self._actor_layers(obs))
 
+    @torch.no_grad()
+    def eval_actor_tapped(self, obs):
+        """eval_actor that also hands out every hidden layer's post-ReLU output: -> (distribution, [H_0 .. H_{L-1}]).  The same GEMMs as
+        eval_actor without gradients, run once; for actors of Linear + ReLU pairs with a log-std that does not depend on the state
+        (learning/unit_stats.py check_model)."""
+        acts = self._trunk_forward(self._actor_layers, obs)
+        mnet = self._action_dist._mean_net
+        mean = torch.addmm(mnet.bias, acts[-1], mnet.weight.t())
+        return DistributionGaussianDiag(mean=mean, logstd=torch.broadcast_to(self._action_dist._logstd_net, mean.shape)), acts[1:]
+
     # ------------------------------------------------------------------ explicit training step (no autograd graph)
     # The update phase runs the same two fixed MLPs 40 times per iteration.  Going through autograd costs, per minibatch, a
     # threshold_backward + a separate bias reduction per layer, an accumulate-into-.grad per parameter and the zeroing of the flat

@@ -1,4 +1,4 @@
-"""Launcher with the reference's run.py flags (run.py:95-164): --env_config --agent_config --mode train|test|record
+"""Launcher with the reference's run.py flags (run.py:95-164): --env_config --agent_config --mode train|test|record|test2
 --num_envs --device --max_samples --out_model_file --int_output_dir --log_file --model_file --rand_seed --test_episodes.
 --mode test|record also take --render_dir DIR [--render_envs 0,1,...] [--render_size WxH]: frames of the rollout as
 DIR/env%04d/frame%06d.png (parc_amd/render.py); without --render_dir nothing is drawn.
@@ -14,6 +14,7 @@ import torch
 from .envs import env_builder
 from .learning import agent_builder
 from .util import arg_parser, mp_util, util
+from .util.logger import Logger
 
 
 def load_args(argv):
@@ -62,6 +63,9 @@ def run(rank, num_procs, master_port, args):
         print("Mean Return: {}\nMean Episode Length: {}\nEpisodes: {}".format(res["mean_return"], res["mean_ep_len"], res["num_eps"]))
     elif mode == "record":
         agent.record_motions()
+    elif mode == "test2":          # test plus the actor's rank / dormant-unit figures (DMPPOAgent.test_model2)
+        res = agent.test_model2(num_episodes=args.parse_int("test_episodes", 16))
+        Logger.print("Mean Return: {}\nMean Episode Length: {}\nEpisodes: {}".format(res["mean_return"], res["mean_ep_len"], res["num_eps"]))
     else:
         raise AssertionError("Unsupported mode: {}".format(mode))
     if writer is not None:
