@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libparc_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip"]
+SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip", "parc_moopt.hip"]
 # The diagnostics library (tools/parc_diag.py; never loaded by this package): the same sources with -DPARC_DIAG_BUILD (timing-ablation bits of
 # parc_track_post_step, the heightmap kernel's measurement knobs) plus the one-env-per-lane reference formulation of the simulator.
 DIAG_LIB_PATH = os.path.join(LIB_DIR, "libparc_hip_diag.so")
@@ -275,6 +275,9 @@ def _declare(L):
     if hasattr(L, "parc_netstats_abi"):
         from . import _hip_netstats
         _hip_netstats.declare(L)
+    if hasattr(L, "parc_moopt_abi"):
+        from . import _hip_moopt
+        _hip_moopt.declare(L)
 
 
 EXPORTED = ["parc_abi_version", "parc_refresh_ray_obs_hfs", "parc_refresh_obs_hfs", "parc_dof_to_rot", "parc_rot_to_dof",
@@ -286,7 +289,9 @@ EXPORTED = ["parc_abi_version", "parc_refresh_ray_obs_hfs", "parc_refresh_obs_hf
             "parc_quat_diff_angle", "parc_quat_diff_angle_grad", "parc_temporal_terms", "parc_temporal_terms_grad", "parc_step_tail",
             "parc_assemble_obs", "parc_track_post_step_timed", "parc_rng_step", "parc_obs_ingest", "parc_action_head_record",
             "parc_render", "parc_render_abi", "parc_motion_score", "parc_score_abi",
-            "parc_netstats_workspace_floats", "parc_netstats_update", "parc_netstats_abs_colsum", "parc_netstats_dormant_count", "parc_netstats_abi"]
+            "parc_netstats_workspace_floats", "parc_netstats_update", "parc_netstats_abs_colsum", "parc_netstats_dormant_count", "parc_netstats_abi",
+            "parc_points_hf_sdf_ragged", "parc_points_hf_sdf_ragged_grad", "parc_temporal_terms_seg", "parc_temporal_terms_seg_grad",
+            "parc_segment_sums", "parc_moopt_abi"]
 
 
 def check(rc, what):

@@ -2,7 +2,7 @@
 
 Mirror of the reference's ``tools/motion_opt/optimize_motions.py`` (config keys of ``tools/motion_opt/config/motion_opt.yaml``:
 motions_yaml_path, device, char_model, output_folder_path, num_iters, step_size, w_*, max_jerk, auto_compute_body_constraints,
-frame_stride, char_point_samples{...}).  Input files are read with the non-executing reader, output files are written in the
+frame_stride, char_point_samples{...}; plus opt_batch_size: clips per descent, absent or 1 = one clip at a time).  Input files are read with the non-executing reader, output files are written in the
 reference's format (util.terrain_util.SubTerrain, tools.motion_opt.motion_optimization.BodyConstraint).
 
 usage:  python -m parc_amd.tools.motion_opt.optimize_motions --config motion_opt.yaml
@@ -79,6 +79,49 @@ def optimize_file(path, cfg, char_model, body_points, output_folder, log_folder)
     return out_path
 
 
+def optimize_files_batch(paths, cfg, char_model, body_points, output_folder, log_folder):
+    """optimize_file for a group of clips in one descent (config key opt_batch_size > 1): the constraints come from
+    compute_approx_body_constraints_batch, the frames from motion_contact_optimization_batch; one output file and one log per clip, named
+    and laid out as optimize_file does."""
+    device = cfg["device"]
+    stride = int(cfg.get("frame_stride", 1))
+    clips = [_load_clip(p, device) for p in paths]
+    names = [os.path.basename(os.path.splitext(p)[0]) + "_opt" for p in paths]
+    body_constraints = None
+    if cfg.get("auto_compute_body_constraints", False):
+        body_constraints = moopt.compute_approx_body_constraints_batch(
+            root_pos=[f[:, 0:3].contiguous() for f, _, _, _ in clips], root_rot=[torch_util.exp_map_to_quat(f[:, 3:6]) for f, _, _, _ in clips],
+            joint_rot=[char_model.dof_to_rot(f[:, 6:].contiguous()) for f, _, _, _ in clips], contacts=[c for _, c, _, _ in clips],
+            char_model=char_model, terrains=[t for _, _, t, _ in clips])
+        for per_motion in body_constraints:
+            for lst in per_motion:
+                for c in lst:
+                    c.start_frame_idx = int(math.ceil(c.start_frame_idx / stride))
+                    c.end_frame_idx = int(math.floor(c.end_frame_idx // stride))
+    frames = [f[::stride].contiguous() for f, _, _, _ in clips]
+    contacts = [c[::stride].contiguous() for _, c, _, _ in clips]
+    w = {k: cfg[k] for k in ("w_root_pos", "w_root_rot", "w_joint_rot", "w_smoothness", "w_penetration", "w_contact", "w_sliding",
+                             "w_body_constraints", "w_jerk")}
+    opt = moopt.motion_contact_optimization_batch(src_frames=frames, contacts=contacts, body_points=body_points, terrains=[t for _, _, t, _ in clips],
+                                                  char_model=char_model, num_iters=cfg["num_iters"], step_size=cfg["step_size"],
+                                                  body_constraints=body_constraints, max_jerk=cfg["max_jerk"], exp_names=names, use_wandb=False,
+                                                  log_files=[os.path.join(log_folder, "log_" + n + ".txt") for n in names], **w)
+    out_paths = []
+    for m, (_, _, terrain, fps) in enumerate(clips):
+        cpu_t = terrain.torch_copy()
+        cpu_t.set_device("cpu")
+        data = {"fps": fps // stride, "loop_mode": "CLAMP", "frames": opt[m].cpu(), "contacts": contacts[m].cpu(), "terrain": cpu_t}
+        if body_constraints is not None:
+            for lst in body_constraints[m]:
+                for c in lst:
+                    c.constraint_point = c.constraint_point.cpu()
+            data["opt:body_constraints"] = body_constraints[m]
+        out_path = os.path.join(output_folder, names[m] + ".pkl")
+        terrain_util.dump_reference_pickle(data, out_path)
+        out_paths.append(out_path)
+    return out_paths
+
+
 def main(argv):
     cfg_path = argv[2] if len(argv) == 3 and argv[1] == "--config" else "tools/motion_opt/config/motion_opt.yaml"
     with open(cfg_path, "r") as f:
@@ -96,6 +139,14 @@ def main(argv):
                                                    capsule_num_sphere_subdivisons=ps["capsule_num_sphere_subdivisions"],
                                                    capsule_num_cylinder_slices=ps["capsule_num_cylinder_slices"])
     t0 = time.time()
+    batch = int(cfg.get("opt_batch_size", 1) or 1)
+    if batch > 1:       # groups of opt_batch_size clips, in order, each group in one descent
+        for i in range(0, len(files), batch):
+            group = files[i:i + batch]
+            print("OPTIMIZING MOTIONS:", ", ".join(os.path.basename(p) for p in group), "{}-{}/{}".format(i, i + len(group) - 1, len(files)))
+            optimize_files_batch(group, cfg, km, body_points, out_folder, log_folder)
+        print("Total optimization time for", len(files), "motions:", time.time() - t0, "seconds.")
+        return
     for i, path in enumerate(files):
         print("OPTIMIZING MOTION:", os.path.basename(path), "{}/{}".format(i, len(files)))
         optimize_file(path, cfg, km, body_points, out_folder, log_folder)

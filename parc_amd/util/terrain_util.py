@@ -399,6 +399,102 @@ class _PointsHfSdf(torch.autograd.Function):
         return g_pts, None, None, None, None, None, None
 
 
+class HfTable:
+    """Heightfields of different sizes and cell sizes behind one device table (parc_moopt_terrain_t), for points_hf_sdf_ragged: one float
+    pool holds every terrain's heights and its cell-centre coordinates - the values HfGrid derives for that terrain alone (its own
+    host-evaluated torch.linspace, its own half cell size) - and the table names each terrain's offsets, dimensions, cell (0, 0) centre
+    and base_z.  Built once per batch of motions; a query reads nothing back from the device."""
+
+    def __init__(self, terrains, base_z=-10.0, device=None):
+        from .. import _hip_moopt
+        terrains = list(terrains)
+        n = len(terrains)
+        base = [float(b) for b in base_z] if isinstance(base_z, (list, tuple)) else [float(base_z)] * n
+        assert len(base) == n
+        dev = device if device is not None else (terrains[0].hf.device if n else "cpu")
+        parts, off = [], 0
+        entries = (_hip_moopt.MooptTerrainS * max(n, 1))()
+        self.shapes = []
+        for k, t in enumerate(terrains):
+            hf = t.hf.detach().to(device="cpu", dtype=torch.float32).contiguous()
+            X, Y = int(hf.shape[0]), int(hf.shape[1])
+            dxdy = t.dxdy.detach().to(torch.float32).cpu()
+            mp = t.min_point.detach().to(torch.float32).cpu()
+            xs = torch.linspace(0.0, (X - 1.0) * dxdy[0].item(), X)
+            ys = torch.linspace(0.0, (Y - 1.0) * dxdy[1].item(), Y)
+            half = dxdy / 2.0
+            e = entries[k]
+            e.off_hf, e.off_x, e.off_y = off, off + X * Y, off + X * Y + X
+            e.dim_x, e.dim_y = X, Y
+            e.ox, e.oy = float(mp[0]), float(mp[1])
+            e.half_x, e.half_y = float(half[0]), float(half[1])
+            e.base_z = base[k]
+            parts += [hf.reshape(-1), xs, ys]
+            off += X * Y + X + Y
+            self.shapes.append((X, Y))
+        assert off < 2 ** 31
+        self.num_terrains = n
+        self.base_z = base
+        self.entries = entries                      # host copy (tests, debugging)
+        self.pool = (torch.cat(parts) if parts else torch.zeros(1)).to(dev).contiguous()
+        raw = np.frombuffer(bytes(entries), dtype=np.uint8).copy()
+        self.table = torch.from_numpy(raw).to(dev).contiguous()
+        self.device = torch.device(dev)
+
+
+def points_hf_sdf_ragged(points, row_terrain, table, inverted=True, radius=None):
+    """Signed distance of points [n_rows, points_per_row, 3] to the heightfield table[row_terrain[row]] of their row (row_terrain int32
+    [n_rows]); the values of points_hf_sdf per terrain, for terrains of any size in one launch (parc_points_hf_sdf_ragged).  A row whose
+    terrain id is outside the table gives NaN.  Differentiable in the points (one launch, parc_points_hf_sdf_ragged_grad)."""
+    assert points.dim() == 3 and points.shape[-1] == 3 and row_terrain.dim() == 1 and row_terrain.shape[0] == points.shape[0]
+    assert row_terrain.dtype == torch.int32
+    if radius is not None:
+        assert isinstance(radius, float) and radius > 0.0
+    if torch.is_grad_enabled() and points.requires_grad:
+        return _PointsHfSdfRagged.apply(points, row_terrain, table, bool(inverted), radius)
+    return _points_hf_sdf_ragged_launch(points, row_terrain, table, inverted, radius, False)[0]
+
+
+def _points_hf_sdf_ragged_launch(points, row_terrain, table, inverted, radius, want_cell):
+    from .. import _hip
+    R, K = int(points.shape[0]), int(points.shape[1])
+    dev = points.device
+    out = torch.empty((R, K), dtype=torch.float32, device=dev)
+    cell = torch.empty((R, K), dtype=torch.int32, device=dev) if want_cell else None
+    pts = points.detach().to(torch.float32).contiguous()
+    if R * K:
+        _hip.check(_hip.lib().parc_points_hf_sdf_ragged(_hip.stream(), R, K, _hip.ptr(pts), _hip.ptr(row_terrain), table.num_terrains, _hip.ptr(table.table),
+                                                        _hip.ptr(table.pool), 1 if inverted else 0, float(radius) if radius is not None else 0.0,
+                                                        _hip.ptr(out), _hip.ptr(cell)), "parc_points_hf_sdf_ragged")
+    return out, cell, pts
+
+
+class _PointsHfSdfRagged(torch.autograd.Function):
+    """points_hf_sdf_ragged for fixed terrains: forward = the query (which also reports the arg-min column), backward =
+    parc_points_hf_sdf_ragged_grad, one launch each."""
+
+    @staticmethod
+    def forward(ctx, points, row_terrain, table, inverted, radius):
+        out, cell, pts = _points_hf_sdf_ragged_launch(points, row_terrain, table, inverted, radius, True)
+        ctx.save_for_backward(pts, row_terrain, cell)
+        ctx.table, ctx.inverted = table, inverted
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        from .. import _hip
+        pts, row_terrain, cell = ctx.saved_tensors
+        table = ctx.table
+        R, K = int(pts.shape[0]), int(pts.shape[1])
+        g = g_out.to(torch.float32).contiguous()
+        g_pts = torch.empty_like(pts)
+        if R * K:
+            _hip.check(_hip.lib().parc_points_hf_sdf_ragged_grad(_hip.stream(), R, K, _hip.ptr(pts), _hip.ptr(row_terrain), table.num_terrains,
+                                                                 _hip.ptr(table.table), _hip.ptr(table.pool), 1 if ctx.inverted else 0, _hip.ptr(cell),
+                                                                 _hip.ptr(g), _hip.ptr(g_pts)), "parc_points_hf_sdf_ragged_grad")
+        return g_pts, None, None, None, None
+
+
 class BodyPoints:
     """The sample points of all bodies as one table: local coordinates [P, 3], owning body [P] and the offsets of each body's
     (contiguous) range - prepared once per character / point set."""

@@ -1,0 +1,303 @@
+"""The batched motion optimiser's kernels behind one interface for tests/test_motion_opt_batch*.py -- TEST INFRASTRUCTURE.
+
+Cases are plain numpy.  They run through the host build of parc_moopt_core.h (moopt_host.cpp, compiled here), through the stand-alone
+program built from the same file with -DMOOPT_HOST_MAIN (plain or with -fsanitize=address,undefined), which reads the case from a
+file, or - in the GPU tests - through the device entry points of include/parc_moopt.h.  Also here: the float64 restatement of the
+seamed frame-to-frame terms, and the three test motions derived from fixture G20.
+"""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+REPO = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, REPO)
+from parc_amd import _hip_moopt      # noqa: E402
+
+SOURCE = os.path.join(HERE, "moopt_host.cpp")
+FLAGS = ["-std=c++17", "-Wall", "-Wextra", "-Wno-unused-function", "-Wno-unknown-pragmas", "-Wno-missing-field-initializers"]
+# the sanitizer runtimes are linked statically: the program then runs whatever else the environment preloads
+SANITIZE = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+C, C2 = 0.03, 0.0009            # pseudo-Huber constants of the sliding term
+
+
+def build_host(out_dir):
+    lib = os.path.join(out_dir, "libparc_moopt_host.so")
+    # -ffp-contract=off: the host build is the plain-fp32 evaluation of the header (no fused multiply-adds)
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-ffp-contract=off", "-fPIC", "-shared"] + FLAGS + ["-o", lib, SOURCE, "-lm"])
+    return lib
+
+
+def build_program(out_dir, sanitize=True):
+    """the stand-alone program (its own main): `prog case_file [out_file]`"""
+    exe = os.path.join(out_dir, "moopt_host_main" + ("_asan" if sanitize else ""))
+    subprocess.check_call([os.environ.get("CXX", "g++")] + (SANITIZE if sanitize else ["-O2"]) + ["-ffp-contract=off", "-DMOOPT_HOST_MAIN"] + FLAGS +
+                          ["-o", exe, SOURCE, "-lm"])
+    return exe
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+_libs = {}
+
+
+def host_lib(path):
+    if path not in _libs:
+        L = ctypes.CDLL(path)
+        for name, args in (("moopt_ragged_host", _hip_moopt.RAGGED_ARGTYPES[1:]), ("moopt_ragged_grad_host", _hip_moopt.RAGGED_GRAD_ARGTYPES[1:]),
+                           ("moopt_tt_seg_host", _hip_moopt.TT_SEG_ARGTYPES[1:]), ("moopt_tt_seg_grad_host", _hip_moopt.TT_SEG_GRAD_ARGTYPES[1:]),
+                           ("moopt_segment_sums_host", _hip_moopt.SEGMENT_SUMS_ARGTYPES[1:])):
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = args
+        _libs[path] = L
+    return _libs[path]
+
+
+def f32(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def segments(lengths):
+    """(seg_start [M + 1], seg_of_frame [N]) int32"""
+    ss = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    return ss, np.repeat(np.arange(len(lengths), dtype=np.int32), lengths)
+
+
+# ---------------------------------------------------------------------------------------------------------- seamed temporal terms
+class TtCase:
+    """packed frames of motions of the given lengths, random masks and a jerk limit that clips part of the frames"""
+
+    def __init__(self, lengths, B, seed):
+        rng = np.random.default_rng(seed)
+        self.lengths, self.B = list(lengths), B
+        self.ss, self.sf = segments(self.lengths)
+        N = self.N = int(self.ss[-1])
+        self.M = len(self.lengths)
+        self.pos = f32(rng.normal(size=(N, B, 3)))
+        self.r = f32(rng.uniform(size=(N, B)))
+        self.sv = f32(0.3 * rng.normal(size=(N, B, 3)))
+        self.keep = f32(rng.uniform(size=(N, B)) > 0.3)
+        self.pc = f32(rng.uniform(size=(N, B)))
+        self.lim = 7.0          # |third difference| of unit normal positions is about 7.7: clips part of the frames
+        self.w = f32(rng.normal(size=(3, self.M)))
+
+    def host(self, path):
+        L = host_lib(path)
+        N, B, M = self.N, self.B, self.M
+        partial, g_pos, g_r = np.full((3, N, B), -7, np.float32), np.full((N, B, 3), -7, np.float32), np.full((N, B), -7, np.float32)
+        rc = L.moopt_tt_seg_host(N, B, M, _p(self.ss), _p(self.sf), _p(self.pos), _p(self.r), _p(self.sv), _p(self.keep), _p(self.pc), C, C2, self.lim,
+                                 _p(partial))
+        assert rc == 0, rc
+        rc = L.moopt_tt_seg_grad_host(N, B, M, _p(self.ss), _p(self.sf), _p(self.pos), _p(self.r), _p(self.sv), _p(self.keep), _p(self.pc), C, C2,
+                                      self.lim, _p(self.w), _p(g_pos), _p(g_r))
+        assert rc == 0, rc
+        return {"partial": partial, "g_pos": g_pos, "g_r": g_r}
+
+    def dump(self, path):
+        with open(path, "wb") as f:
+            f.write(i32([1, self.N, self.B, self.M, 0, 0, 0, 0]).tobytes())
+            f.write(f32([C, C2, self.lim, 0]).tobytes())
+            for a in (self.ss, self.sf, self.pos, self.r, self.sv, self.keep, self.pc, self.w):
+                f.write(a.tobytes())
+
+    def read_program_output(self, path):
+        raw = np.fromfile(path, dtype=np.float32)
+        n = self.N * self.B
+        assert raw.size == 7 * n
+        return {"partial": raw[:3 * n].reshape(3, self.N, self.B), "g_pos": raw[3 * n:6 * n].reshape(self.N, self.B, 3), "g_r": raw[6 * n:].reshape(self.N, self.B)}
+
+    def sums(self, partial):
+        """[3, M] in float64 from per-(frame, body) partials"""
+        return np.array([[partial[k, self.ss[m]:self.ss[m + 1]].astype(np.float64).sum() for m in range(self.M)] for k in range(3)])
+
+    def float64(self):
+        """the three sums per motion [3, M] and the adjoint for the cotangents self.w, motion by motion, in float64 (the torch
+        expressions of the single path, restated)"""
+        sums = np.zeros((3, self.M))
+        g_pos, g_r = np.zeros((self.N, self.B, 3)), np.zeros((self.N, self.B))
+        for m, T in enumerate(self.lengths):
+            s = int(self.ss[m])
+            pos, r, sv, keep, pc = (x[s:s + T].astype(np.float64) for x in (self.pos, self.r, self.sv, self.keep, self.pc))
+            w0, w1, w2 = (float(x) for x in self.w[:, m])
+            gp = np.zeros_like(pos)
+            if T >= 2:
+                e = pos[1:] - pos[:-1] - sv[:-1]
+                e2 = (e * e).sum(-1)
+                k, c, rr = keep[:-1], pc[:-1], r[:-1]
+                sums[0, m] = e2.sum() + rr.sum()
+                sums[1, m] = ((np.sqrt(k * e2 + C2) - C) * c).sum() + ((np.sqrt(k * rr + C2) - C) * c).sum()
+                f = (2.0 * w0 + w1 * c * k / np.sqrt(k * e2 + C2))[..., None] * e
+                gp[1:] += f
+                gp[:-1] -= f
+                g_r[s:s + T - 1] = w0 + w1 * c * k / (2.0 * np.sqrt(k * rr + C2))
+            if T >= 4:
+                v = pos[1:] - pos[:-1]
+                a = v[1:] - v[:-1]
+                j = a[1:] - a[:-1]
+                jn = np.linalg.norm(j, axis=-1)
+                sums[2, m] = np.clip(jn - self.lim, 0.0, None).sum()
+                d = np.where((jn > self.lim)[..., None], w2 * j / np.maximum(jn, 1e-300)[..., None], 0.0)
+                for off, coef in ((0, -1.0), (1, 3.0), (2, -3.0), (3, 1.0)):
+                    gp[off:off + T - 3] += coef * d
+            g_pos[s:s + T] = gp
+        return sums, g_pos, g_r
+
+
+# ---------------------------------------------------------------------------------------------------------- ragged terrain query
+def table_of(terrains, base_z):
+    """terrains: list of (hf [X, Y], min_point [2], dxdy [2]) numpy -> (ctypes table, pool float32): HfTable's layout, restated"""
+    import torch
+    entries = (_hip_moopt.MooptTerrainS * max(len(terrains), 1))()
+    parts, off = [], 0
+    for k, (hf, mp, dxdy) in enumerate(terrains):
+        X, Y = hf.shape
+        dxdy = f32(dxdy)
+        xs, ys = torch.linspace(0.0, (X - 1.0) * float(dxdy[0]), X).numpy(), torch.linspace(0.0, (Y - 1.0) * float(dxdy[1]), Y).numpy()
+        e = entries[k]
+        e.off_hf, e.off_x, e.off_y, e.dim_x, e.dim_y = off, off + X * Y, off + X * Y + X, X, Y
+        e.ox, e.oy = float(mp[0]), float(mp[1])
+        e.half_x, e.half_y = float(dxdy[0] / np.float32(2)), float(dxdy[1] / np.float32(2))
+        e.base_z = float(base_z)
+        parts += [f32(hf).reshape(-1), xs, ys]
+        off += X * Y + X + Y
+    return entries, f32(np.concatenate(parts))
+
+
+class RaggedCase:
+    """Three terrains (23 x 17 at 0.4 x 0.25, 1 x 1, 10 x 10 at 0.4 x 0.4), rows interleaved between them (skip=1: between terrains 0
+    and 2 only, so that terrain 1 owns no row); points hundreds of cells away, near, on the border, one with a NaN coordinate, one row
+    with terrain id -1 and one with id 3."""
+    K = 8       # points per row
+
+    def __init__(self, seed=9, skip=None):
+        rng = np.random.default_rng(seed)
+        self.terrains = [(f32(rng.uniform(-1, 1, size=(23, 17))), f32([0.3, -0.2]), f32([0.4, 0.25])),
+                         (f32([[0.25]]), f32([1.0, 0.5]), f32([0.5, 0.25])),
+                         (f32(rng.uniform(-0.5, 0.5, size=(10, 10))), f32([-0.64, -0.66]), f32([0.4, 0.4]))]
+        K = self.K
+        far = rng.uniform(-400, 400, size=(12, K, 3))
+        near = np.stack([rng.uniform(-1, 10, size=(24, K)), rng.uniform(-1, 5, size=(24, K)), rng.uniform(-3, 3, size=(24, K))], axis=-1)
+        X, Y = 23, 17
+        edge = np.array([[0.3, -0.2, 0.0], [0.3 + 0.4 * (X - 1), -0.2 + 0.25 * (Y - 1), 5.0], [0.3 - 0.2, -0.2 - 0.125, -20.0], [0.5, 0.05, 1e6],
+                         [1.0, 0.5, 0.25], [1.25, 0.625, 0.25], [-0.64, -0.66, 0.0], [-0.64 + 3.6, -0.66 + 3.6, 0.1]])
+        pts = np.concatenate([far, near, edge.reshape(1, K, 3).repeat(3, axis=0)], axis=0)
+        R = pts.shape[0]
+        rt = np.arange(R) % 3                                   # interleaved between terrains 0, 1, 2
+        self.nan_at = (14, 3)
+        pts[self.nan_at] = [np.nan, 0.2, 0.1]
+        self.bad_rows = (5, 20)
+        if skip is not None:
+            rt[rt == skip] = (skip + 1) % 3
+        rt[5], rt[20] = -1, 3
+        self.points, self.row_terrain, self.R = f32(pts), i32(rt), R
+        self.g_out = f32(rng.normal(size=(R, K)))
+
+    def table(self, base_z=-10.0):
+        return table_of(self.terrains, base_z)
+
+    def valid_rows(self, t):
+        return np.nonzero(self.row_terrain == t)[0]
+
+    def host(self, path, inverted, radius, base_z=-10.0):
+        L = host_lib(path)
+        entries, pool = self.table(base_z)
+        R, K = self.R, self.K
+        out, cell, g = np.full((R, K), -7, np.float32), np.full((R, K), -7, np.int32), np.full((R, K, 3), -7, np.float32)
+        rc = L.moopt_ragged_host(R, K, _p(self.points), _p(self.row_terrain), len(self.terrains), ctypes.cast(entries, ctypes.c_void_p), _p(pool),
+                                 1 if inverted else 0, radius or 0.0, _p(out), _p(cell))
+        assert rc == 0, rc
+        rc = L.moopt_ragged_grad_host(R, K, _p(self.points), _p(self.row_terrain), len(self.terrains), ctypes.cast(entries, ctypes.c_void_p), _p(pool),
+                                      1 if inverted else 0, _p(cell), _p(self.g_out), _p(g))
+        assert rc == 0, rc
+        return {"out": out, "cell": cell, "g_points": g}
+
+    def oracle(self, orc, inverted, radius, base_z=-10.0):
+        """per terrain through oracle.points_hf_sdf -> {terrain: (rows, values [rows, K])}"""
+        res = {}
+        kw = {} if radius is None else {"radius": radius}
+        for t in range(3):
+            rows = self.valid_rows(t)
+            hf, mp, dxdy = self.terrains[t]
+            with np.errstate(invalid="ignore"):
+                res[t] = (rows, orc.points_hf_sdf(self.points[rows].reshape(1, -1, 3), hf[None], mp[None], dxdy, base_z=base_z, inverted=inverted,
+                                                  **kw).reshape(len(rows), self.K))
+        return res
+
+    def dump(self, path, inverted, radius, base_z=-10.0):
+        entries, pool = self.table(base_z)
+        with open(path, "wb") as f:
+            f.write(i32([2, self.R, self.K, len(self.terrains), 1 if inverted else 0, pool.size, 0, 0]).tobytes())
+            f.write(f32([radius or 0.0, 0, 0, 0]).tobytes())
+            for a in (self.points, self.row_terrain):
+                f.write(a.tobytes())
+            f.write(bytes(entries))
+            f.write(pool.tobytes())
+            f.write(self.g_out.tobytes())
+
+    def read_program_output(self, path):
+        raw = np.fromfile(path, dtype=np.float32)
+        n = self.R * self.K
+        assert raw.size == 5 * n
+        return {"out": raw[:n].reshape(self.R, self.K), "cell": raw[n:2 * n].view(np.int32).reshape(self.R, self.K),
+                "g_points": raw[2 * n:].reshape(self.R, self.K, 3)}
+
+
+# ---------------------------------------------------------------------------------------------------------- segment sums
+def segment_sums_host(path, values, seg_start):
+    L = host_lib(path)
+    values, seg_start = f32(values), i32(seg_start)
+    P, R, W = values.shape
+    M = seg_start.size - 1
+    out = np.full((P, M), -7, np.float32)
+    rc = L.moopt_segment_sums_host(P, R, W, M, _p(seg_start), _p(values), _p(out))
+    assert rc == 0, rc
+    return out
+
+
+def dump_segment_sums(path, values, seg_start):
+    values, seg_start = f32(values), i32(seg_start)
+    P, R, W = values.shape
+    with open(path, "wb") as f:
+        f.write(i32([3, P, R, W, seg_start.size - 1, 0, 0, 0]).tobytes())
+        f.write(f32([0, 0, 0, 0]).tobytes())
+        f.write(seg_start.tobytes())
+        f.write(values.tobytes())
+
+
+# ---------------------------------------------------------------------------------------------------------- the three test motions
+def g20():
+    return np.load(os.path.join(REPO, "tests", "golden", "g20_motion_opt.npz"))
+
+
+def clip_constraint_rows(rows, first, last):
+    """G20's constraint rows [body, start, end, x, y, z] clipped to frames first..last and re-indexed to the window"""
+    out = []
+    for r in rows:
+        s, e = max(int(r[1]), first), min(int(r[2]), last)
+        if s <= e:
+            out.append([r[0], s - first, e - first, r[3], r[4], r[5]])
+    return np.array(out, dtype=np.float64).reshape(-1, 6)
+
+
+def three_motions(g=None):
+    """A = G20 as it is; B = frames 5..16 on G20's heights padded by one zero column on each side in y and cut to the first 7 rows (min
+    point moved by -dy in y), G20's constraints clipped to the window; C = frames 20..23 on a one-cell field, no constraints.
+    -> list of dicts(frames, tgt, contacts, hf, min_point, dxdy, rows | None)"""
+    g = g20() if g is None else g
+    A = dict(frames=g["src_frames"], tgt=g["tgt_frames"], contacts=g["contacts"], hf=g["hf"], min_point=g["min_point"], dxdy=g["dxdy"],
+             rows=g["body_constraints"])
+    hf_b = np.pad(g["hf"], ((0, 0), (1, 1)))[:7]
+    B = dict(frames=g["src_frames"][5:17], tgt=g["tgt_frames"][5:17], contacts=g["contacts"][5:17], hf=f32(hf_b),
+             min_point=f32([g["min_point"][0], g["min_point"][1] - g["dxdy"][1]]), dxdy=g["dxdy"], rows=clip_constraint_rows(g["body_constraints"], 5, 16))
+    C = dict(frames=g["src_frames"][20:24], tgt=g["tgt_frames"][20:24], contacts=g["contacts"][20:24], hf=f32([[0.1]]),
+             min_point=f32([g["src_frames"][20, 0], g["src_frames"][20, 1]]), dxdy=f32([0.5, 0.25]), rows=None)
+    return [A, B, C]
