@@ -13,6 +13,11 @@ call it unchanged.  What differs is the mechanics:
 * nothing in an iteration reads the device back (the reference takes nine ``.item()`` per iteration for its loss dict); the terms
   are read at the logging stride only, so a whole iteration (forward, backward, Adam) is captured ONCE in a hipGraph and replayed.
 
+``motion_contact_optimization_batch`` / ``compute_approx_body_constraints_batch`` do the same for M motions, each on its own terrain, in
+one descent.  The single and the batch path share everything around the loss evaluation: the constraint row tables
+(``pack_constraint_rows``, ``_ProblemTables``), the source poses (``_source_poses``), the contact runs (``_contact_runs``) and the descent
+driver with its capture protocol and logs (``_descend``).  The two ``evaluate`` bodies are separate on purpose: their reductions differ.
+
 Checked against fixture G20 (the reference's loss terms, gradient, body constraints and a 40-iteration descent).
 """
 import enum
@@ -99,9 +104,8 @@ def _project_points_to_surface(points, terrain, num_iters=1000, lr=0.01):
     return p.detach()
 
 
-def compute_approx_body_constraints(root_pos, root_rot, joint_rot, contacts, char_model, terrain):
-    """Per body a list of BodyConstraint: for feet and hands, every run of frames labelled "in contact" (> 0.9) becomes one
-    constraint at the run's mean body position, projected onto the terrain surface."""
+def _contact_runs(root_pos, root_rot, joint_rot, contacts, char_model):
+    """the (body, frame run, mean body position) triples compute_approx_body_constraints projects, for one motion"""
     body_pos, body_rot = char_model.forward_kinematics(root_pos, root_rot, joint_rot)
     ids = {n: char_model.get_body_id(n) for n in ("left_foot", "right_foot", "left_hand", "right_hand")}
     pos = {}
@@ -110,64 +114,64 @@ def compute_approx_body_constraints(root_pos, root_rot, joint_rot, contacts, cha
         if n.endswith("foot"):       # the centre of the foot box, not the ankle (:136-142)
             off = _f32(char_model.get_geoms(b)[0]._offset, body_pos.device)
             pos[n] = pos[n] + torch_util.quat_rotate(body_rot[:, b], off.unsqueeze(0).expand(body_pos.shape[0], 3))
+    return [(b, r, pos[n][r].mean(dim=0)) for n, b in ids.items() for r in _consecutive_true_runs(contacts[:, b] > 0.9)]
+
+
+def _add_constraint(per_body, body, start, end, point):
+    c = BodyConstraint()
+    c.start_frame_idx, c.end_frame_idx, c.constraint_point = int(start), int(end), point
+    per_body[body].append(c)
+
+
+def compute_approx_body_constraints(root_pos, root_rot, joint_rot, contacts, char_model, terrain):
+    """Per body a list of BodyConstraint: for feet and hands, every run of frames labelled "in contact" (> 0.9) becomes one
+    constraint at the run's mean body position, projected onto the terrain surface."""
     out = [[] for _ in range(char_model.get_num_joints())]
     # every run of every body becomes one point; all of them descend together (independent terms of one objective)
-    todo = [(b, r, pos[n][r].mean(dim=0)) for n, b in ids.items() for r in _consecutive_true_runs(contacts[:, b] > 0.9)]
+    todo = _contact_runs(root_pos, root_rot, joint_rot, contacts, char_model)
     if todo:
         pts = _project_points_to_surface(torch.stack([p for _, _, p in todo]), terrain)
         for k, (b, r, _) in enumerate(todo):
-            c = BodyConstraint()
-            c.start_frame_idx = r[0].item()
-            c.end_frame_idx = r[-1].item()
-            c.constraint_point = pts[k].clone()
-            out[b].append(c)
+            _add_constraint(out, b, r[0].item(), r[-1].item(), pts[k].clone())
     return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the loss (reference :183-395)
+# the tables of a problem: motions packed along the frame axis (one motion is the case M = 1)
 # ---------------------------------------------------------------------------------------------------------------------
-class _Problem:
-    """Everything of one optimisation problem that does not change between evaluations, laid out once on the device: the sample
-    points of all bodies as one [P, 3] table with their owner, the heightfield grid, contact weights, and the body constraints
-    as index ranges.  evaluate() touches the device only through launches (capturable)."""
+def pack_segments(lengths):
+    """-> (seg_start [M + 1], seg_of_frame [sum T]) as Python lists: motion m owns packed frames seg_start[m] .. seg_start[m + 1] - 1"""
+    seg_start, seg_of_frame = [0], []
+    for m, t in enumerate(lengths):
+        t = int(t)
+        assert t >= 0
+        seg_start.append(seg_start[-1] + t)
+        seg_of_frame += [m] * t
+    return seg_start, seg_of_frame
 
-    def __init__(self, src_root_pos, src_root_rot_quat, src_joint_rot, src_body_vels, src_body_rot_vels, contacts, terrain, body_points,
-                 char_model, body_constraints):
-        dev = src_root_pos.device
-        self.km = char_model
-        self.src = (src_root_pos, src_root_rot_quat, src_joint_rot, src_body_vels, src_body_rot_vels)
-        self.contacts = contacts
-        B = char_model.get_num_joints()
-        assert len(body_points) == B
-        self.points = terrain_util.BodyPoints(body_points, dev)
-        counts = self.points.counts
-        self.local, self.owner = self.points.local, self.points.owner
-        self.start = self.points.start[:B]
-        self.counts = counts
-        self.hf = terrain.hf.to(dev, torch.float32).unsqueeze(0)
-        self.min_point = terrain.min_point.to(dev, torch.float32).unsqueeze(0)
-        self.dxdy = terrain.dxdy
-        self.grid = terrain_util.HfGrid(self.hf, terrain.dxdy, dev)
-        # contact present in both frames of a pair, negative labels (generator artefacts) clipped (:232-234)
-        self.pair_contact = torch.clamp(torch.minimum(contacts[1:], contacts[:-1]), min=0.0)
-        T = int(src_root_pos.shape[0])
-        # per-body closest point: the bodies' point ranges padded to one width (a repeated point does not change a minimum)
-        pmax = max(counts)
-        assert min(counts) > 0, "every body needs at least one sample point"
-        self.body_pts = torch.tensor([[self.start[b] + min(k, counts[b] - 1) for k in range(pmax)] for b in range(B)], dtype=torch.int64, device=dev)
-        # body constraints as flat row tables, one row per (constraint, frame[, sole point]): frame index, body / point index,
-        # constraint point, radius[, geom offset].  The frame pairs a constraint covers are exempt from the sliding term (:328-333).
-        sph = {"f": [], "b": [], "pt": [], "r": [], "off": []}
-        box = {"f": [], "p": [], "pt": [], "r": []}
-        keep = torch.ones((T - 1, B), dtype=torch.float32, device=dev)
-        if body_constraints is not None:
+
+def pack_constraint_rows(char_model, body_constraints, lengths, point_start, point_counts):
+    """Body constraints of M motions as flat row tables, one row per (constraint, frame[, sole point]): frame index (offset by the motion's
+    seg_start), body / point index, constraint point, radius[, geom offset].  Pure Python, no device: -> (sph, box, keep, sph_seg, box_seg).
+    sph / box: dicts of lists (f, b | p, pt, r[, off]) in motion order, so that motion m owns rows sph_seg[m] .. sph_seg[m + 1] - 1
+    (box_seg likewise); keep: [sum T][B] nested list, 0 where a constraint covers (frame, body) - those pairs are exempt from the sliding
+    term (:328-333) - within the motion's own rows only."""
+    B = char_model.get_num_joints()
+    seg_start, _ = pack_segments(lengths)
+    sph = {"f": [], "b": [], "pt": [], "r": [], "off": []}
+    box = {"f": [], "p": [], "pt": [], "r": []}
+    keep = [[1.0] * B for _ in range(seg_start[-1])]
+    sph_seg, box_seg = [0], [0]
+    for m, T in enumerate(lengths):
+        T, o = int(T), seg_start[m]
+        bc = body_constraints[m] if body_constraints is not None else None
+        if bc is not None:
             for b in range(B):
-                for c in body_constraints[b]:
+                for c in bc[b]:
                     geom = char_model.get_geoms(b)[0]
                     s, e = int(c.start_frame_idx), int(c.end_frame_idx)
                     point = _f32(c.constraint_point, "cpu").reshape(3).tolist()
-                    fr = list(range(s, min(e, T - 1) + 1))
+                    fr = [o + f for f in range(s, min(e, T - 1) + 1)]
                     if geom._shape_type == kin_char_model.GeomType.SPHERE:
                         radius = float(_f32(geom._dims, "cpu").reshape(-1)[0])
                         off = _f32(geom._offset, "cpu").reshape(3).tolist()
@@ -178,21 +182,65 @@ class _Problem:
                         sph["off"] += [off] * len(fr)
                     elif geom._shape_type == kin_char_model.GeomType.BOX:
                         radius = float(torch.linalg.vector_norm(_f32(geom._dims, "cpu"))) * 1.25
-                        assert counts[b] >= 18, "the sole of a box body is its first 18 sample points"
+                        assert point_counts[b] >= 18, "the sole of a box body is its first 18 sample points"
                         for f in fr:
                             box["f"] += [f] * 18
-                            box["p"] += list(range(self.start[b], self.start[b] + 18))
+                            box["p"] += list(range(point_start[b], point_start[b] + 18))
                         box["pt"] += [point] * (18 * len(fr))
                         box["r"] += [radius] * (18 * len(fr))
                     else:
                         continue
-                    keep[s:e + 1, b] = 0.0
+                    for f in range(max(s, 0), min(e + 1, T)):       # never beyond the motion's own rows
+                        keep[o + f][b] = 0.0
+        sph_seg.append(len(sph["f"]))
+        box_seg.append(len(box["f"]))
+    return sph, box, keep, sph_seg, box_seg
+
+
+class _ProblemTables:
+    """What an optimisation problem of one motion and one of M packed motions lay out alike, once, on the device: the sample points of all
+    bodies as one [P, 3] table with their owner, each body's point range padded to one width, and the body constraints as row tables."""
+
+    def _build_tables(self, char_model, body_points, body_constraints, lengths, dev):
+        """body_constraints: per motion a constraint list or None -> (sph_seg, box_seg) of pack_constraint_rows"""
+        B = char_model.get_num_joints()
+        self.km = char_model
+        self.points = terrain_util.BodyPoints(body_points, dev)
+        counts, start = self.points.counts, self.points.start[:B]
+        assert len(body_points) == B and min(counts) > 0, "every body needs at least one sample point"
+        # per-body closest point: the bodies' point ranges padded to one width (a repeated point does not change a minimum)
+        self.body_pts = torch.tensor([[start[b] + min(k, counts[b] - 1) for k in range(max(counts))] for b in range(B)], dtype=torch.int64, device=dev)
+        sph, box, keep, sph_seg, box_seg = pack_constraint_rows(char_model, body_constraints, lengths, start, counts)
         i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
         f32 = lambda v, w_: torch.tensor(v, dtype=torch.float32, device=dev).reshape(-1, w_) if w_ else torch.tensor(v, dtype=torch.float32, device=dev)
         self.sph = (i64(sph["f"]), i64(sph["b"]), f32(sph["pt"], 3), f32(sph["r"], 0), f32(sph["off"], 3)) if sph["f"] else None
         self.box = (i64(box["f"]), i64(box["p"]), f32(box["pt"], 3), f32(box["r"], 0)) if box["f"] else None
-        self.pair_keep = keep
-        self.has_constraints = body_constraints is not None
+        self.pair_keep = torch.tensor(keep, dtype=torch.float32, device=dev).reshape(sum(lengths), B)
+        return sph_seg, box_seg
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the loss (reference :183-395)
+# ---------------------------------------------------------------------------------------------------------------------
+class _Problem(_ProblemTables):
+    """Everything of one optimisation problem that does not change between evaluations, laid out once on the device: the tables of
+    _ProblemTables, the heightfield grid and the contact weights.  evaluate() touches the device only through launches (capturable)."""
+
+    def __init__(self, src_root_pos, src_root_rot_quat, src_joint_rot, src_body_vels, src_body_rot_vels, contacts, terrain, body_points,
+                 char_model, body_constraints):
+        dev = src_root_pos.device
+        self.src = (src_root_pos, src_root_rot_quat, src_joint_rot, src_body_vels, src_body_rot_vels)
+        self.contacts = contacts
+        T = int(src_root_pos.shape[0])
+        self._build_tables(char_model, body_points, [body_constraints], [T], dev)
+        self.pair_keep = self.pair_keep[:T - 1]          # one row per frame pair
+        self.local = self.points.local
+        self.hf = terrain.hf.to(dev, torch.float32).unsqueeze(0)
+        self.min_point = terrain.min_point.to(dev, torch.float32).unsqueeze(0)
+        self.dxdy = terrain.dxdy
+        self.grid = terrain_util.HfGrid(self.hf, terrain.dxdy, dev)
+        # contact present in both frames of a pair, negative labels (generator artefacts) clipped (:232-234)
+        self.pair_contact = torch.clamp(torch.minimum(contacts[1:], contacts[:-1]), min=0.0)
 
     def evaluate(self, tgt_root_pos, tgt_root_rot, tgt_joint_dof, w, max_jerk):
         """-> (weighted total, the nine terms stacked in _TERM_ORDER)"""
@@ -325,65 +373,22 @@ def build_logger(log_file, exp_name=None, use_wandb=True):
     return log
 
 
-def motion_contact_optimization(src_frames, contacts, body_points, terrain, char_model, num_iters, step_size, w_root_pos, w_root_rot, w_joint_rot,
-                                w_smoothness, w_penetration, w_contact, w_sliding, w_body_constraints, w_jerk, body_constraints, max_jerk, exp_name,
-                                use_wandb, log_file, use_graph=None, verbose=True, loss_trace=None):
-    """Adam on (root position, root exponential map, joint dofs) of every frame; returns the optimised frames [T, 34].
-    use_graph (default: on a GPU): capture one iteration in a hipGraph after three eager ones and replay it.
-    loss_trace: optional list that receives the total loss of every iteration as ONE device tensor at the end (tests)."""
-    start_time = time.time()
-    dev = src_frames.device
-    src_frames = src_frames.to(torch.float32)
-    contacts = contacts.to(torch.float32)
-    with torch.no_grad():
-        src_root_pos = src_frames[:, 0:3]
-        src_root_rot_quat = torch_util.exp_map_to_quat(src_frames[:, 3:6])
-        src_joint_rot = char_model.dof_to_rot(src_frames[:, 6:34].contiguous())
-        src_body_pos, src_body_rot = char_model.forward_kinematics(src_root_pos.contiguous(), src_root_rot_quat, src_joint_rot)
-        src_body_vels = src_body_pos[1:] - src_body_pos[:-1]
-        src_body_rot_vels = torch_util.quat_diff_angle(src_body_rot[1:], src_body_rot[:-1])
-    prob = _Problem(src_root_pos, src_root_rot_quat, src_joint_rot, src_body_vels, src_body_rot_vels, contacts, terrain, body_points, char_model,
-                    body_constraints)
-    w = _weights(w_root_pos=w_root_pos, w_root_rot=w_root_rot, w_joint_rot=w_joint_rot, w_smoothness=w_smoothness, w_penetration=w_penetration,
-                 w_contact=w_contact, w_sliding=w_sliding, w_body_constraints=w_body_constraints, w_jerk=w_jerk)
-    params = [src_frames[:, 0:3].clone().requires_grad_(True), src_frames[:, 3:6].clone().requires_grad_(True),
-              src_frames[:, 6:34].clone().requires_grad_(True)]
-    on_gpu = src_frames.is_cuda
-    use_graph = on_gpu if use_graph is None else use_graph
-    # one multi-tensor launch per step on the GPU (same update rule)
-    optimizer = torch.optim.Adam(params, lr=step_size, capturable=bool(use_graph), **({"fused": True} if on_gpu else {}))
-    log_iter_stride = 25
-    logger = build_logger(log_file=log_file, exp_name=exp_name, use_wandb=use_wandb)
-    # the iteration's outputs live in fixed buffers: [total, nine terms]
-    record = torch.zeros(1 + len(_TERM_ORDER), dtype=torch.float32, device=dev)
-    trace = torch.zeros(max(num_iters, 1), dtype=torch.float32, device=dev) if loss_trace is not None else None
-    it_idx = torch.zeros((), dtype=torch.int64, device=dev)
+def _source_poses(char_model, frames):
+    """frames [n, 34] -> (root pos, root quat, joint rot, body pos, body rot) of the source frames"""
+    root_pos = frames[:, 0:3].contiguous()
+    root_quat = torch_util.exp_map_to_quat(frames[:, 3:6])
+    joint_rot = char_model.dof_to_rot(frames[:, 6:34].contiguous())
+    body_pos, body_rot = char_model.forward_kinematics(root_pos, root_quat, joint_rot)
+    return root_pos, root_quat, joint_rot, body_pos, body_rot
 
-    def iteration():
-        optimizer.zero_grad(set_to_none=True)
-        loss, terms = prob.evaluate(params[0], params[1], params[2], w, max_jerk)
-        loss.backward()
-        optimizer.step()
-        with torch.no_grad():
-            record[0] = loss.detach()
-            record[1:] = terms.detach()
-            if trace is not None:
-                trace.index_copy_(0, it_idx.reshape(1), loss.detach().reshape(1))
-                it_idx.add_(1)
 
-    def log_now(it):
-        vals = record.tolist()
-        logger.log("Iteration", it)
-        logger.log("Time (min)", (time.time() - start_time) / 60.0)
-        logger.log("TOTAL WEIGHTED LOSS", vals[0])
-        for key, val in zip(_TERM_ORDER, vals[1:]):
-            logger.log(key.name, val)
-        if verbose:
-            logger.print_log()
-        logger.write_log()
-
+def _descend(iteration, num_iters, use_graph, record, loggers, verbose, start_time, trace=None, loss_trace=None):
+    """Run `iteration` num_iters times: eagerly, or (use_graph) three times on a side stream, then captured once in a hipGraph and
+    replayed.  `iteration` leaves its results in the fixed buffer `record` [1 + nine terms, len(loggers)] (row 0 the total, then
+    _TERM_ORDER; one column per logger); every 25 iterations the record is read back once and each column goes to its logger.  Closes
+    the loggers' files and hands trace[:num_iters] to loss_trace.  Adds no launch, copy or synchronise to the iterations."""
     graph = None
-    warm = 3
+    warm, log_iter_stride = 3, 25
     for it in range(num_iters):
         if use_graph and it == warm:
             graph = torch.cuda.CUDAGraph()
@@ -403,12 +408,67 @@ def motion_contact_optimization(src_frames, contacts, body_points, terrain, char
         else:
             iteration()
         if it % log_iter_stride == 0:
-            log_now(it)
-    if getattr(logger, "_file", None) is not None:
-        logger._file.close()
-        logger._file = None
+            vals = record.t().tolist()          # the one read-back of the stride
+            for logger, v in zip(loggers, vals):
+                logger.log("Iteration", it)
+                logger.log("Time (min)", (time.time() - start_time) / 60.0)
+                logger.log("TOTAL WEIGHTED LOSS", v[0])
+                for key, val in zip(_TERM_ORDER, v[1:]):
+                    logger.log(key.name, val)
+                if verbose:
+                    logger.print_log()
+                logger.write_log()
+    for logger in loggers:
+        if getattr(logger, "_file", None) is not None:
+            logger._file.close()
+            logger._file = None
     if loss_trace is not None:
         loss_trace.append(trace[:num_iters].clone())
+
+
+def motion_contact_optimization(src_frames, contacts, body_points, terrain, char_model, num_iters, step_size, w_root_pos, w_root_rot, w_joint_rot,
+                                w_smoothness, w_penetration, w_contact, w_sliding, w_body_constraints, w_jerk, body_constraints, max_jerk, exp_name,
+                                use_wandb, log_file, use_graph=None, verbose=True, loss_trace=None):
+    """Adam on (root position, root exponential map, joint dofs) of every frame; returns the optimised frames [T, 34].
+    use_graph (default: on a GPU): capture one iteration in a hipGraph after three eager ones and replay it.
+    loss_trace: optional list that receives the total loss of every iteration as ONE device tensor at the end (tests)."""
+    start_time = time.time()
+    dev = src_frames.device
+    src_frames = src_frames.to(torch.float32)
+    contacts = contacts.to(torch.float32)
+    with torch.no_grad():
+        src_root_pos, src_root_rot_quat, src_joint_rot, src_body_pos, src_body_rot = _source_poses(char_model, src_frames)
+        src_body_vels = src_body_pos[1:] - src_body_pos[:-1]
+        src_body_rot_vels = torch_util.quat_diff_angle(src_body_rot[1:], src_body_rot[:-1])
+    prob = _Problem(src_root_pos, src_root_rot_quat, src_joint_rot, src_body_vels, src_body_rot_vels, contacts, terrain, body_points, char_model,
+                    body_constraints)
+    w = _weights(w_root_pos=w_root_pos, w_root_rot=w_root_rot, w_joint_rot=w_joint_rot, w_smoothness=w_smoothness, w_penetration=w_penetration,
+                 w_contact=w_contact, w_sliding=w_sliding, w_body_constraints=w_body_constraints, w_jerk=w_jerk)
+    params = [src_frames[:, 0:3].clone().requires_grad_(True), src_frames[:, 3:6].clone().requires_grad_(True),
+              src_frames[:, 6:34].clone().requires_grad_(True)]
+    on_gpu = src_frames.is_cuda
+    use_graph = on_gpu if use_graph is None else use_graph
+    # one multi-tensor launch per step on the GPU (same update rule)
+    optimizer = torch.optim.Adam(params, lr=step_size, capturable=bool(use_graph), **({"fused": True} if on_gpu else {}))
+    logger = build_logger(log_file=log_file, exp_name=exp_name, use_wandb=use_wandb)
+    # the iteration's outputs live in fixed buffers: [total, nine terms]
+    record = torch.zeros(1 + len(_TERM_ORDER), dtype=torch.float32, device=dev)
+    trace = torch.zeros(max(num_iters, 1), dtype=torch.float32, device=dev) if loss_trace is not None else None
+    it_idx = torch.zeros((), dtype=torch.int64, device=dev)
+
+    def iteration():
+        optimizer.zero_grad(set_to_none=True)
+        loss, terms = prob.evaluate(params[0], params[1], params[2], w, max_jerk)
+        loss.backward()
+        optimizer.step()
+        with torch.no_grad():
+            record[0] = loss.detach()
+            record[1:] = terms.detach()
+            if trace is not None:
+                trace.index_copy_(0, it_idx.reshape(1), loss.detach().reshape(1))
+                it_idx.add_(1)
+
+    _descend(iteration, num_iters, use_graph, record.unsqueeze(1), [logger], verbose, start_time, trace, loss_trace)
     return torch.cat([p.detach() for p in params], dim=-1)
 
 
@@ -420,63 +480,6 @@ def motion_contact_optimization(src_frames, contacts, body_points, terrain, char
 # things need to know about the packing: the terrain query (a terrain per frame: terrain_util.points_hf_sdf_ragged) and the
 # frame-to-frame terms (cut at the seams: parc_temporal_terms_seg).  Per-motion loss terms for the logs come from parc_segment_sums.
 # ---------------------------------------------------------------------------------------------------------------------
-def pack_segments(lengths):
-    """-> (seg_start [M + 1], seg_of_frame [sum T]) as Python lists: motion m owns packed frames seg_start[m] .. seg_start[m + 1] - 1"""
-    seg_start, seg_of_frame = [0], []
-    for m, t in enumerate(lengths):
-        t = int(t)
-        assert t >= 0
-        seg_start.append(seg_start[-1] + t)
-        seg_of_frame += [m] * t
-    return seg_start, seg_of_frame
-
-
-def pack_constraint_rows(char_model, body_constraints, lengths, point_start, point_counts):
-    """The constraint row tables of _Problem for M motions, frame indices offset by seg_start (pure Python, no device):
-    -> (sph, box, keep, sph_seg, box_seg).  sph / box: dicts of lists (f, b | p, pt, r[, off]) in motion order, so that motion m owns
-    rows sph_seg[m] .. sph_seg[m + 1] - 1 (box_seg likewise); keep: [sum T][B] nested list, 0 where a constraint covers (frame, body)
-    - within the motion's own rows only."""
-    B = char_model.get_num_joints()
-    seg_start, _ = pack_segments(lengths)
-    sph = {"f": [], "b": [], "pt": [], "r": [], "off": []}
-    box = {"f": [], "p": [], "pt": [], "r": []}
-    keep = [[1.0] * B for _ in range(seg_start[-1])]
-    sph_seg, box_seg = [0], [0]
-    for m, T in enumerate(lengths):
-        T, o = int(T), seg_start[m]
-        bc = body_constraints[m] if body_constraints is not None else None
-        if bc is not None:
-            for b in range(B):
-                for c in bc[b]:
-                    geom = char_model.get_geoms(b)[0]
-                    s, e = int(c.start_frame_idx), int(c.end_frame_idx)
-                    point = _f32(c.constraint_point, "cpu").reshape(3).tolist()
-                    fr = [o + f for f in range(s, min(e, T - 1) + 1)]
-                    if geom._shape_type == kin_char_model.GeomType.SPHERE:
-                        radius = float(_f32(geom._dims, "cpu").reshape(-1)[0])
-                        off = _f32(geom._offset, "cpu").reshape(3).tolist()
-                        sph["f"] += fr
-                        sph["b"] += [b] * len(fr)
-                        sph["pt"] += [point] * len(fr)
-                        sph["r"] += [radius] * len(fr)
-                        sph["off"] += [off] * len(fr)
-                    elif geom._shape_type == kin_char_model.GeomType.BOX:
-                        radius = float(torch.linalg.vector_norm(_f32(geom._dims, "cpu"))) * 1.25
-                        assert point_counts[b] >= 18, "the sole of a box body is its first 18 sample points"
-                        for f in fr:
-                            box["f"] += [f] * 18
-                            box["p"] += list(range(point_start[b], point_start[b] + 18))
-                        box["pt"] += [point] * (18 * len(fr))
-                        box["r"] += [radius] * (18 * len(fr))
-                    else:
-                        continue
-                    for f in range(max(s, 0), min(e + 1, T)):       # never beyond the motion's own rows
-                        keep[o + f][b] = 0.0
-        sph_seg.append(len(sph["f"]))
-        box_seg.append(len(box["f"]))
-    return sph, box, keep, sph_seg, box_seg
-
-
 def segment_sums(values, seg_start, num_segments, out=None):
     """values [n_planes, n_rows, width] -> [n_planes, num_segments]: sums over each segment's rows and all columns, in an order fixed by
     the segment's own layout (parc_segment_sums); seg_start: int32 device tensor [num_segments + 1]"""
@@ -530,7 +533,7 @@ class _TemporalTermsSeg(torch.autograd.Function):
         return g_pos, g_r[:ctx.r_rows], None, None, None, None, None, None
 
 
-class _BatchProblem:
+class _BatchProblem(_ProblemTables):
     """_Problem for M motions packed along the frame axis: the same tables, with frame indices offset by seg_start, one terrain table
     for the ragged query and the segment tables the per-motion sums need.  evaluate() touches the device only through launches, and
     their number does not depend on M."""
@@ -540,8 +543,7 @@ class _BatchProblem:
         assert M >= 1 and len(contacts) == M and len(terrains) == M
         dev = src_frames[0].device
         assert dev.type == "cuda", "the batched optimiser runs on the GPU (its kernels have no CPU fallback)"
-        self.km, self.M = char_model, M
-        B = char_model.get_num_joints()
+        self.M = M
         self.lengths = [int(f.shape[0]) for f in src_frames]
         assert min(self.lengths) >= 1
         seg_start, seg_of_frame = pack_segments(self.lengths)
@@ -555,10 +557,7 @@ class _BatchProblem:
         last = torch.zeros(N, dtype=torch.bool, device=dev)
         last[[s - 1 for s in seg_start[1:]]] = True
         with torch.no_grad():
-            s_rp = frames[:, 0:3].contiguous()
-            s_rq = torch_util.exp_map_to_quat(frames[:, 3:6])
-            s_jr = char_model.dof_to_rot(frames[:, 6:34].contiguous())
-            bp, br = char_model.forward_kinematics(s_rp, s_rq, s_jr)
+            s_rp, s_rq, s_jr, bp, br = _source_poses(char_model, frames)
             # frame-to-frame sources, one row per packed frame; the last row of every motion is zero (and never read)
             nxt = torch.clamp(torch.arange(N, device=dev) + 1, max=N - 1)
             s_bv = torch.where(last[:, None, None], torch.zeros_like(bp), bp[nxt] - bp).contiguous()
@@ -566,21 +565,10 @@ class _BatchProblem:
             pc = torch.clamp(torch.minimum(self.contacts[nxt], self.contacts), min=0.0)      # :232-234, per pair
             self.pair_contact = torch.where(last[:, None], torch.zeros_like(pc), pc).contiguous()
         self.src = (s_rp, s_rq, s_jr, s_bv, s_brv)
-        self.points = terrain_util.BodyPoints(body_points, dev)
-        counts = self.points.counts
-        assert len(body_points) == B and min(counts) > 0, "every body needs at least one sample point"
-        start = self.points.start[:B]
-        pmax = max(counts)
-        self.body_pts = torch.tensor([[start[b] + min(k, counts[b] - 1) for k in range(pmax)] for b in range(B)], dtype=torch.int64, device=dev)
         # the descent's queries use the base_z of the single path (-10.0) for every terrain
         self.table = terrain_util.HfTable(terrains, base_z=-10.0, device=dev)
-        sph, box, keep, sph_seg, box_seg = pack_constraint_rows(char_model, body_constraints, self.lengths, start, counts)
-        i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
-        f32 = lambda v, w_: torch.tensor(v, dtype=torch.float32, device=dev).reshape(-1, w_) if w_ else torch.tensor(v, dtype=torch.float32, device=dev)
-        self.sph = (i64(sph["f"]), i64(sph["b"]), f32(sph["pt"], 3), f32(sph["r"], 0), f32(sph["off"], 3)) if sph["f"] else None
-        self.box = (i64(box["f"]), i64(box["p"]), f32(box["pt"], 3), f32(box["r"], 0)) if box["f"] else None
+        sph_seg, box_seg = self._build_tables(char_model, body_points, body_constraints, self.lengths, dev)
         self.sph_seg, self.box_seg = i32(sph_seg), i32(box_seg)
-        self.pair_keep = torch.tensor(keep, dtype=torch.float32, device=dev).reshape(N, B).contiguous()
         self._cot = {}
 
     def _const(self, key, like, value):
@@ -695,7 +683,6 @@ def motion_contact_optimization_batch(src_frames, contacts, body_points, terrain
     params = [frames[:, 0:3].clone().requires_grad_(True), frames[:, 3:6].clone().requires_grad_(True), frames[:, 6:34].clone().requires_grad_(True)]
     use_graph = True if use_graph is None else use_graph
     optimizer = torch.optim.Adam(params, lr=step_size, capturable=bool(use_graph), fused=True)
-    log_iter_stride = 25
     loggers = [build_logger(log_file=log_files[m], exp_name=exp_names[m], use_wandb=use_wandb) for m in range(M)]
     # the iteration's outputs live in fixed buffers: row 0 the totals, rows 1..9 the nine terms, one column per motion
     record = torch.zeros((1 + len(_TERM_ORDER), M), dtype=torch.float32, device=dev)
@@ -712,60 +699,10 @@ def motion_contact_optimization_batch(src_frames, contacts, body_points, terrain
                 trace.index_copy_(0, it_idx.reshape(1), totals.reshape(1, M))
                 it_idx.add_(1)
 
-    def log_now(it):
-        vals = record.t().tolist()          # the one read-back of the stride
-        for m, logger in enumerate(loggers):
-            logger.log("Iteration", it)
-            logger.log("Time (min)", (time.time() - start_time) / 60.0)
-            logger.log("TOTAL WEIGHTED LOSS", vals[m][0])
-            for key, val in zip(_TERM_ORDER, vals[m][1:]):
-                logger.log(key.name, val)
-            if verbose:
-                logger.print_log()
-            logger.write_log()
-
-    graph = None
-    warm = 3
-    for it in range(num_iters):
-        if use_graph and it == warm:
-            graph = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graph):
-                iteration()
-        if graph is not None:
-            graph.replay()
-        elif use_graph:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                iteration()
-            torch.cuda.current_stream().wait_stream(side)
-        else:
-            iteration()
-        if it % log_iter_stride == 0:
-            log_now(it)
-    for logger in loggers:
-        if getattr(logger, "_file", None) is not None:
-            logger._file.close()
-            logger._file = None
-    if loss_trace is not None:
-        loss_trace.append(trace[:num_iters].clone())
+    _descend(iteration, num_iters, use_graph, record, loggers, verbose, start_time, trace, loss_trace)
     out = torch.cat([p.detach() for p in params], dim=-1)
     s = prob.seg_start_list
     return [out[s[m]:s[m + 1]].clone() for m in range(M)]
-
-
-def _contact_runs(root_pos, root_rot, joint_rot, contacts, char_model):
-    """the (body, frame run, mean body position) triples compute_approx_body_constraints projects, for one motion"""
-    body_pos, body_rot = char_model.forward_kinematics(root_pos, root_rot, joint_rot)
-    ids = {n: char_model.get_body_id(n) for n in ("left_foot", "right_foot", "left_hand", "right_hand")}
-    pos = {}
-    for n, b in ids.items():
-        pos[n] = body_pos[:, b]
-        if n.endswith("foot"):
-            off = _f32(char_model.get_geoms(b)[0]._offset, body_pos.device)
-            pos[n] = pos[n] + torch_util.quat_rotate(body_rot[:, b], off.unsqueeze(0).expand(body_pos.shape[0], 3))
-    return [(b, r, pos[n][r].mean(dim=0)) for n, b in ids.items() for r in _consecutive_true_runs(contacts[:, b] > 0.9)]
 
 
 def compute_approx_body_constraints_batch(root_pos, root_rot, joint_rot, contacts, char_model, terrains, num_iters=1000, lr=0.01):
@@ -800,8 +737,5 @@ def compute_approx_body_constraints_batch(root_pos, root_rot, joint_rot, contact
     pts = p.reshape(-1, 3).cpu()
     ends = [(int(r[0]), int(r[-1])) for r in torch.stack([torch.stack([x[2][0], x[2][-1]]) for x in flat]).cpu().tolist()]
     for k, (m, b, _, _) in enumerate(flat):
-        c = BodyConstraint()
-        c.start_frame_idx, c.end_frame_idx = ends[k]
-        c.constraint_point = pts[k].clone().to(dev)
-        out[m][b].append(c)
+        _add_constraint(out[m], b, ends[k][0], ends[k][1], pts[k].clone().to(dev))
     return out

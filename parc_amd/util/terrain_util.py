@@ -401,8 +401,8 @@ class _PointsHfSdf(torch.autograd.Function):
 
 class HfTable:
     """Heightfields of different sizes and cell sizes behind one device table (parc_moopt_terrain_t), for points_hf_sdf_ragged: one float
-    pool holds every terrain's heights and its cell-centre coordinates - the values HfGrid derives for that terrain alone (its own
-    host-evaluated torch.linspace, its own half cell size) - and the table names each terrain's offsets, dimensions, cell (0, 0) centre
+    pool holds every terrain's heights and its cell-centre coordinates - HfGrid of that terrain alone, which also gives its half cell
+    size - and the table names each terrain's offsets, dimensions, cell (0, 0) centre
     and base_z.  Built once per batch of motions; a query reads nothing back from the device."""
 
     def __init__(self, terrains, base_z=-10.0, device=None):
@@ -417,19 +417,16 @@ class HfTable:
         self.shapes = []
         for k, t in enumerate(terrains):
             hf = t.hf.detach().to(device="cpu", dtype=torch.float32).contiguous()
-            X, Y = int(hf.shape[0]), int(hf.shape[1])
-            dxdy = t.dxdy.detach().to(torch.float32).cpu()
+            grid = HfGrid(hf, t.dxdy, "cpu")
+            X, Y = grid.shape
             mp = t.min_point.detach().to(torch.float32).cpu()
-            xs = torch.linspace(0.0, (X - 1.0) * dxdy[0].item(), X)
-            ys = torch.linspace(0.0, (Y - 1.0) * dxdy[1].item(), Y)
-            half = dxdy / 2.0
             e = entries[k]
             e.off_hf, e.off_x, e.off_y = off, off + X * Y, off + X * Y + X
             e.dim_x, e.dim_y = X, Y
             e.ox, e.oy = float(mp[0]), float(mp[1])
-            e.half_x, e.half_y = float(half[0]), float(half[1])
+            e.half_x, e.half_y = grid.half
             e.base_z = base[k]
-            parts += [hf.reshape(-1), xs, ys]
+            parts += [hf.reshape(-1), grid.xs, grid.ys]
             off += X * Y + X + Y
             self.shapes.append((X, Y))
         assert off < 2 ** 31

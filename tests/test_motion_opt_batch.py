@@ -236,18 +236,6 @@ def test_exports_and_documentation():
 
 
 # ------------------------------------------------------------------------------------------------------ packing logic (pure Python)
-class _C:
-    def __init__(self, row):
-        self.start_frame_idx, self.end_frame_idx, self.constraint_point = int(row[1]), int(row[2]), np.asarray(row[3:6], np.float32)
-
-
-def _constraints(km, rows):
-    out = [[] for _ in range(km.get_num_joints())]
-    for r in (rows if rows is not None else []):
-        out[int(r[0])].append(_C(r))
-    return out if rows is not None else None
-
-
 def test_packing_logic():
     import motion_score_ref as ref
     from parc_amd.anim import kin_char_model
@@ -266,7 +254,7 @@ def test_packing_logic():
     assert mo.pack_segments([3, 0, 1]) == ([0, 3, 3, 4], [0, 0, 0, 2])
     counts = [int(n) for n in g["pts_count"]]
     start = [sum(counts[:b]) for b in range(len(counts))]
-    bcs = [_constraints(km, m["rows"]) for m in (A, B, C)]
+    bcs = [mh.constraints_from_rows(m["rows"], 15) for m in (A, B, C)]
     sph, box, keep, sph_seg, box_seg = mo.pack_constraint_rows(km, bcs, lengths, start, counts)
     keep = np.array(keep)
     assert keep.shape == (56, 15)
@@ -290,9 +278,95 @@ def test_packing_logic():
                 want[ss[m] + int(r[1]):ss[m] + min(int(r[2]) + 1, lengths[m]), int(r[0])] = 0
     assert np.array_equal(keep, want) and (keep == 0).any()
     # a constraint that runs past its motion's end stays inside the motion
-    over = [[] for _ in range(15)]
-    over[int(A["rows"][0][0])].append(_C([A["rows"][0][0], 2, 99, 0, 0, 0]))
+    over = mh.constraints_from_rows([[A["rows"][0][0], 2, 99, 0, 0, 0]], 15)
     s2, b2, k2, _, _ = mo.pack_constraint_rows(km, [over, None], [4, 3], start, counts)
     assert max(s2["f"] + b2["f"]) == 3 and (np.array(k2)[4:] == 1).all()
     # the sphere / box split of the single path: feet are boxes (18 sole points per frame), hands are spheres
     assert len(box["f"]) % 18 == 0 and len(box["f"]) > 0 and len(sph["f"]) > 0
+
+
+def _tables(mo, km, bc, T, start, counts):
+    """pack_constraint_rows for one motion as the tensors _Problem holds: (sph | None, box | None, keep[:T - 1])"""
+    import torch
+    sph, box, keep, sph_seg, box_seg = mo.pack_constraint_rows(km, [bc], [T], start, counts)
+    assert sph_seg == [0, len(sph["f"])] and box_seg == [0, len(box["f"])]
+    i64, f32 = (lambda v: torch.tensor(v, dtype=torch.int64)), (lambda v, shape: torch.tensor(v, dtype=torch.float32).reshape(shape))
+    n, k = len(sph["f"]), len(box["f"])
+    return ((i64(sph["f"]), i64(sph["b"]), f32(sph["pt"], (n, 3)), f32(sph["r"], (n,)), f32(sph["off"], (n, 3))) if n else None,
+            (i64(box["f"]), i64(box["p"]), f32(box["pt"], (k, 3)), f32(box["r"], (k,))) if k else None,
+            torch.tensor(keep, dtype=torch.float32).reshape(T, 15)[:T - 1])
+
+
+def test_single_problem_holds_the_packers_tables():
+    """_Problem (built on the CPU: its constructor launches nothing) against pack_constraint_rows for that motion alone: the sphere and
+    box row tables and the sliding mask, value for value, with the shapes and dtypes evaluate() reads"""
+    import motion_score_ref as ref
+    import torch
+    from parc_amd.tools.motion_opt import motion_optimization as mo
+    from parc_amd.util import terrain_util
+    km = ref.humanoid()
+    g = mh.g20()
+    counts = [int(n) for n in g["pts_count"]]
+    start = [sum(counts[:b]) for b in range(len(counts))]
+    pts = [torch.tensor(p, dtype=torch.float32) for p in np.split(g["pts"], np.cumsum(counts)[:-1])]
+    A, B, C = mh.three_motions(g)
+    bodies = sorted({int(r[0]) for r in A["rows"]})
+    over = mh.constraints_from_rows([[b, 2, 99, 0.1 * b, 0.0, 0.2] for b in bodies], 15)      # runs past the end of a 4-frame motion
+    cases = [("A", A, mh.constraints_from_rows(A["rows"], 15), 40, 7, 684), ("B", B, mh.constraints_from_rows(B["rows"], 15), 12, 7, 198),
+             ("C", C, None, 4, 0, 0), ("over", C, over, 4, None, None)]
+    for name, mot, bc, T, n_sph, n_box in cases:
+        fr = torch.tensor(mot["frames"], dtype=torch.float32)
+        assert fr.shape == (T, 34)
+        ter = terrain_util.SubTerrain.from_arrays(mot["hf"], mot["min_point"], mot["dxdy"], device="cpu")
+        prob = mo._Problem(fr[:, 0:3], None, None, None, None, torch.tensor(mot["contacts"], dtype=torch.float32), ter, pts, km, bc)
+        sph, box, keep = _tables(mo, km, bc, T, start, counts)
+        for what, have, want in (("sph", prob.sph, sph), ("box", prob.box, box)):
+            assert (have is None) == (want is None), (name, what)
+            if want is not None:
+                n = want[0].shape[0]
+                assert len(have) == len(want) and all(torch.equal(a, b) for a, b in zip(have, want)), (name, what)
+                assert [x.dtype for x in have] == [torch.int64, torch.int64] + [torch.float32] * (len(have) - 2), (name, what)
+                assert [tuple(x.shape) for x in have] == [(n,), (n,), (n, 3), (n,), (n, 3)][:len(have)], (name, what)
+        assert torch.equal(prob.pair_keep, keep) and prob.pair_keep.dtype == torch.float32 and tuple(prob.pair_keep.shape) == (T - 1, 15), name
+        if n_sph is not None:
+            assert (0 if sph is None else sph[0].shape[0], 0 if box is None else box[0].shape[0]) == (n_sph, n_box), name
+        else:
+            assert int(max(prob.sph[0].max(), prob.box[0].max())) == 3 and (prob.pair_keep[2, bodies] == 0).all() and (prob.pair_keep[:2] == 1).all()
+            assert prob.sph[0].shape[0] > 0 and prob.box[0].shape[0] > 0 and prob.box[0].shape[0] % 18 == 0
+
+
+@pytest.mark.parametrize("M", [1, 3])
+@pytest.mark.parametrize("num_iters", [0, 1, 26, 51])
+def test_descent_driver_with_a_stub_iteration(tmp_path, M, num_iters):
+    """_descend run eagerly on the CPU: the iteration runs num_iters times, every logger's file gets the header and one row for iterations
+    0, 25, 50 as far as they exist, holding its own column of the record as it stood after that iteration, and is closed on return.
+    The stub's record entries are small integers: the log's 8 digits hold them exactly."""
+    import torch
+    from parc_amd.tools.motion_opt import motion_optimization as mo
+    counter = torch.zeros((), dtype=torch.int64)
+    rows = 1 + len(mo._TERM_ORDER)
+    # M = 1 is the single path's layout: a one-dimensional record, seen by the driver as one column
+    record = torch.zeros(rows if M == 1 else (rows, M), dtype=torch.float32)
+    offset = (1000.0 * torch.arange(M)[None, :] + 10.0 * torch.arange(rows)[:, None]).reshape(record.shape)
+
+    def iteration():
+        counter.add_(1)
+        record.copy_(offset + counter)
+
+    files = [str(tmp_path / ("log_%d.txt" % m)) for m in range(M)]
+    loggers = [mo.build_logger(f) for f in files]
+    handles = [lg._file for lg in loggers]
+    assert all(not h.closed for h in handles)
+    mo._descend(iteration, num_iters, False, record.unsqueeze(1) if M == 1 else record, loggers, False, 0.0)
+    assert counter.item() == num_iters
+    assert all(h.closed for h in handles) and all(lg._file is None for lg in loggers)
+    logged = [it for it in (0, 25, 50) if it < num_iters]
+    for m, f in enumerate(files):
+        lines = [ln.split("\t") for ln in open(f).read().split("\n") if ln.strip()]
+        if not logged:
+            assert lines == []
+            continue
+        assert lines[0] == ["Iteration", "Time (min)", "TOTAL WEIGHTED LOSS"] + [k.name for k in mo._TERM_ORDER]
+        assert [float(r[0]) for r in lines[1:]] == [float(it) for it in logged]
+        for r, it in zip(lines[1:], logged):
+            assert [float(v) for v in r[2:]] == [1000.0 * m + 10.0 * k + it + 1 for k in range(rows)], (m, it, r)

@@ -10,7 +10,7 @@ import torch
 
 from conftest import golden
 from test_hip_parity import DEV, T, close, km  # noqa: F401  (km is a fixture)
-from test_motion_opt_gpu import _constraints_from_rows, _problem, _source_terms
+from test_motion_opt_gpu import _problem, _source_terms
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import moopt_host as mh      # noqa: E402
@@ -161,7 +161,7 @@ class _Batch:
         self.tgt = [T(m["tgt"]) for m in self.motions]
         self.con = [T(m["contacts"]) for m in self.motions]
         self.ter = [_subterrain(m["hf"], m["min_point"], m["dxdy"]) for m in self.motions]
-        self.bc = [(_constraints_from_rows(mo, m["rows"], km.get_num_joints()) if m["rows"] is not None else None) for m in self.motions]
+        self.bc = [mh.constraints_from_rows(m["rows"], km.get_num_joints(), DEV) for m in self.motions]
 
     def pick(self, ids):
         return dict(src_frames=[self.src[i] for i in ids], contacts=[self.con[i] for i in ids], terrains=[self.ter[i] for i in ids],
@@ -285,6 +285,18 @@ def test_launches_per_iteration_do_not_depend_on_m(batch):
         counts[len(ids)] = _kernel_count(run)
     print("kernel launches per evaluation:", counts)
     assert counts[1] == counts[3] and counts[1] > 20, counts
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_capture_protocol_of_the_shared_driver(use_graph):
+    """_descend with a stub iteration that adds 1 to a one-element device counter: the counter ends at num_iters on both sides of the
+    three warm-up iterations (3 never captures; 4 captures and replays once) - a capture records and does not run"""
+    from parc_amd.tools.motion_opt import motion_optimization as mo
+    for num_iters in (0, 1, 3, 4, 10):
+        counter = torch.zeros(1, dtype=torch.int64, device=DEV)
+        record = torch.zeros((1 + len(mo._TERM_ORDER), 1), dtype=torch.float32, device=DEV)
+        mo._descend(lambda: counter.add_(1), num_iters, use_graph, record, [mo.build_logger(None)], False, 0.0)
+        assert counter.item() == num_iters, (use_graph, num_iters, counter.item())
 
 
 def test_logs_go_to_each_motions_own_file(batch, tmp_path):

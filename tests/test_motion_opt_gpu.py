@@ -1,12 +1,18 @@
 """Stage 2's motion optimiser against fixture G20, which the REFERENCE's tools/motion_opt/motion_optimization.py
 produced on CPU (tests/golden/gen_golden.py stage motion-opt): body constraints from contact labels (:34-181), the nine loss terms +
 total + autograd gradient (:183-395) and a 40-iteration Adam descent (:404-500)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden
 from test_hip_parity import DEV, T, close, km  # noqa: F401  (km is a fixture)
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import moopt_host as mh      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,16 +29,6 @@ def _problem(g):
     ter = terrain_util.SubTerrain.from_arrays(g["hf"], g["min_point"], g["dxdy"], device=DEV)
     w = dict(zip(W_NAMES, [float(v) for v in g["weights"][:9]]))
     return pts, ter, w, float(g["weights"][9])
-
-
-def _constraints_from_rows(mo, rows, num_bodies):
-    out = [[] for _ in range(num_bodies)]
-    for r in rows:
-        c = mo.BodyConstraint()
-        c.start_frame_idx, c.end_frame_idx = int(r[1]), int(r[2])
-        c.constraint_point = T(r[3:6].astype(np.float32))
-        out[int(r[0])].append(c)
-    return out
 
 
 def _source_terms(km, src):
@@ -66,7 +62,7 @@ def test_g20_loss_terms_and_gradient(km, case):
     g = golden("g20_motion_opt")
     pts, ter, w, max_jerk = _problem(g)
     src, con, tgt = T(g["src_frames"]), T(g["contacts"]), T(g["tgt_frames"])
-    bc = _constraints_from_rows(mo, g["body_constraints"], km.get_num_joints()) if case == "full" else None
+    bc = mh.constraints_from_rows(g["body_constraints"], km.get_num_joints(), DEV) if case == "full" else None
     if case == "nocon":
         w = dict(w, w_contact=0.0, w_sliding=0.0)
     a, b, c = (tgt[:, 0:3].clone().requires_grad_(True), tgt[:, 3:6].clone().requires_grad_(True), tgt[:, 6:].clone().requires_grad_(True))
@@ -98,7 +94,7 @@ def test_g20_descent_follows_the_reference(km):
     from parc_amd.tools.motion_opt import motion_optimization as mo
     g = golden("g20_motion_opt")
     pts, ter, w, max_jerk = _problem(g)
-    bc = _constraints_from_rows(mo, g["body_constraints"], km.get_num_joints())
+    bc = mh.constraints_from_rows(g["body_constraints"], km.get_num_joints(), DEV)
     ref = g["opt_loss_trace"]
     assert ref[-1] < 0.5 * ref[0]                                    # the descent does reduce the loss
     moved = np.abs(g["opt_frames"] - g["src_frames"]).max()

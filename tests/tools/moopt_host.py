@@ -278,6 +278,21 @@ def g20():
     return np.load(os.path.join(REPO, "tests", "golden", "g20_motion_opt.npz"))
 
 
+def constraints_from_rows(rows, num_bodies, device="cpu"):
+    """constraint rows [body, start, end, x, y, z] -> per body a list of BodyConstraint with its point on `device`; None for rows None"""
+    import torch
+    from parc_amd.tools.motion_opt.motion_optimization import BodyConstraint
+    if rows is None:
+        return None
+    out = [[] for _ in range(num_bodies)]
+    for r in rows:
+        c = BodyConstraint()
+        c.start_frame_idx, c.end_frame_idx = int(r[1]), int(r[2])
+        c.constraint_point = torch.tensor(np.asarray(r[3:6], np.float32), device=device)
+        out[int(r[0])].append(c)
+    return out
+
+
 def clip_constraint_rows(rows, first, last):
     """G20's constraint rows [body, start, end, x, y, z] clipped to frames first..last and re-indexed to the window"""
     out = []
