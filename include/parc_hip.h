@@ -316,7 +316,10 @@ int parc_update_fail_rates(void *stream, int n_envs, int n_motions, const int64_
 
 /* ---- K16/K17: rl_util.compute_td_lambda_return  learning/rl_util.py:6-29  (time-major [T,N]) and the
  * advantage normalisation of DMPPOAgent._build_train_data  learning/dm_ppo_agent.py:393-403.
- * workspace: >= 3*1024 doubles (device), zeroing not required. */
+ * workspace: >= 3*1024 doubles (device), zeroing not required.
+ * Non-finite input as the reference's torch code: fewer than two samples with rand_action_mask == 1, or a NaN / Inf among their
+ * advantages, give a NaN std (mean_std_out too) and with it NaN in every element of norm_adv; a NaN return or value of an unselected
+ * sample stays in its element.  A finite result is what it was before that rule. */
 int parc_td_lambda_return(void *stream, int T, int N, const float *reward, const float *next_vals, const int32_t *done,
                           float discount, float td_lambda, float *ret);
 int parc_adv_normalize(void *stream, int n, const float *ret, const float *vals, const float *rand_action_mask,
@@ -328,7 +331,11 @@ int parc_adv_normalize(void *stream, int n, const float *ret, const float *vals,
  * mean, norm_a [B,A]; logstd [A]; old_logp, adv, mask, pred, tar_val [B].
  * Outputs: g_mean [B,A] = dloss/dmean, g_logstd [A], g_pred [B];
  * out[11] = loss, critic_loss, actor_loss, clip_frac, imp_ratio, action_bound_loss, entropy, reg_loss, cnt, (2 scale factors).
- * workspace: parc_ppo_workspace_floats(B) floats. */
+ * workspace: parc_ppo_workspace_floats(B) floats.
+ * Rows with mask != 1 are SELECTED OUT, as the reference's boolean index does: whatever they hold (NaN, an overflowed ratio), they add
+ * exactly 0 to every term and their g_mean row is 0.  A NaN in mean / norm_a / old_logp / adv of a row with mask == 1 makes actor_loss and
+ * loss NaN (torch.clamp and torch.minimum keep a NaN), that row of g_mean and all of g_logstd NaN; a NaN tar_val makes critic_loss, loss and
+ * its g_pred element NaN.  cnt == 0: the means over an empty selection are 0 / 0. */
 typedef struct {
     float clip_ratio, bound_w, entropy_w, reg_w, critic_w, large_critic_loss;
     int32_t critic_l1;
@@ -368,6 +375,9 @@ int parc_rng_step(void *stream, uint64_t seed, uint64_t *state, float *uniform_o
 /* K20 in two passes over flat buffers (MPOptimizer.step, learning/mp_optimizer.py:20-40: clip_grad_norm_ then SGD with momentum):
  * norm = |grad|_2 (fixed summation order), coef = min(max_norm / (norm + 1e-6), 1) (max_norm <= 0: no clipping), g' = coef grad
  * (+ weight_decay * p), momentum_buf = momentum * momentum_buf + g', params -= lr * momentum_buf.  grad is left as it was.
+ * A NaN norm gives a NaN coef (torch clamps it with clamp(max = 1), which keeps a NaN): params and momentum_buf become NaN in every
+ * element, as after clip_grad_norm_; with max_norm <= 0 a NaN gradient element stays in its element.  The same holds for
+ * parc_adamw_step (exp_avg and exp_avg_sq too) and parc_scale_by_clipped_norm.
  * grad 16-byte aligned; workspace: parc_sgd_workspace_floats() floats; norm_out (may be NULL): the gradient norm. */
 int64_t parc_sgd_workspace_floats(void);
 int parc_sgd_momentum_step(void *stream, int64_t n, float *params, const float *grad, float *momentum_buf, float max_norm, float lr,
@@ -385,7 +395,8 @@ int parc_sgd_momentum_step(void *stream, int64_t n, float *params, const float *
 int parc_adamw_step(void *stream, int64_t n, float *params, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t step,
                     float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, float *workspace, float *norm_out);
 
-/* ---- K12: Normalizer.normalize  learning/normalizer.py:60-63 in one pass: out = clamp((x - mean) / std, -clip, clip).
+/* ---- K12: Normalizer.normalize  learning/normalizer.py:60-63 in one pass: out = clamp((x - mean) / std, -clip, clip) as torch.clamp
+ * has it: bit-identical on finite values, NaN where the quotient is NaN (NaN in x, mean or std, 0 / 0), +-clip for +-inf.
  * x, out [rows, dim] row-major, mean / std [dim]; dim a multiple of 4, 16-byte aligned pointers; out may alias x. */
 int parc_normalize_clamp(void *stream, int64_t rows, int dim, const float *x, const float *mean, const float *stdv, float clip, float *out);
 
@@ -394,7 +405,7 @@ int parc_normalize_clamp(void *stream, int64_t rows, int dim, const float *x, co
  * workspace: parc_moments_workspace_floats(rows, dim) floats of scratch (caller-owned). */
 int64_t parc_moments_workspace_floats(int64_t rows, int dim);
 int parc_moments_accumulate(void *stream, int64_t rows, int dim, const float *x, float *acc, float *workspace);
-/* The three passes a rollout step makes over its observation rows in one: norm_out = parc_normalize_clamp(x) (bit-identical);
+/* The three passes a rollout step makes over its observation rows in one: norm_out = parc_normalize_clamp(x) (bit-identical, NaN for NaN);
  * copy_dst (may be NULL): x is also written into time row *copy_row (device int64) of a [T, rows, dim] buffer - ExperienceBuffer.record
  * experience_buffer.py:55-59; acc (may be NULL): parc_moments_accumulate(x) with the same partial rows and summation order
  * (workspace as there).  All pointers 16-byte aligned, dim a multiple of 4. */
@@ -431,7 +442,8 @@ int parc_points_hf_sdf_grad(void *stream, int batch, int n_points, int dim_x, in
                             float base_z, int inverted, const int32_t *cell, const float *g_out, float *g_points);
 
 /* Backward of a Linear + ReLU layer between its two GEMMs (the derivative of learning/nets/fc_3layers_2048units.py:4-22): in one pass
- * gy[r, c] <- gy[r, c] * (y[r, c] > 0) (in place) and db[c] <- sum_r of the result (overwritten, fixed summation order).
+ * gy[r, c] <- (y[r, c] <= 0 ? 0 : gy[r, c]) (in place; aten.threshold_backward: gy passes at a NaN activation) and db[c] <- sum_r of
+ * the result (overwritten, fixed summation order).
  * gy, y: [rows, dim] row-major, dim % 4 == 0, 16-byte aligned; workspace: parc_relu_bwd_workspace_floats(rows, dim) floats. */
 int64_t parc_relu_bwd_workspace_floats(int64_t rows, int dim);
 int parc_relu_bwd_bias_grad(void *stream, int64_t rows, int dim, float *gy, const float *y, float *db, float *workspace);

@@ -2010,7 +2010,10 @@ extern "C" int parc_td_lambda_return(void *stream, int T, int N, const float *re
 }
 
 // =============================================================================================
-// K17 advantage normalisation: deterministic two-stage (sum, sumsq, count) in fp64, then normalise
+// K17 advantage normalisation: deterministic two-stage (sum, sumsq, count) in fp64, then normalise.
+// Non-finite input as torch.std_mean / clamp_min / clamp (dm_ppo_agent.py:393-400): no selected sample -> mean and std NaN, one -> std
+// NaN, a NaN or Inf among the selected advantages -> both NaN (torch's running mean meets inf - inf); a NaN std makes every advantage
+// NaN; a NaN return or value of an unselected sample stays in its element.
 // =============================================================================================
 #define ADV_BLOCKS 1024
 __global__ __launch_bounds__(256) void adv_partial_kernel(int n, const float *__restrict__ ret, const float *__restrict__ vals,
@@ -2066,17 +2069,19 @@ __global__ __launch_bounds__(256) void adv_apply_kernel(int n, int nblocks, cons
         __syncthreads();
     }
     double cnt = sh[2][0];
-    double mean = cnt > 0.0 ? sh[0][0] / cnt : 0.0;
-    double var = cnt > 1.0 ? fmax((sh[1][0] - cnt * mean * mean) / (cnt - 1.0), 0.0) : 0.0;  // torch.std_mean: unbiased
+    double mean = sh[0][0] / cnt;                                          // (cnt 0: 0 / 0)
+    double var = (sh[1][0] - cnt * mean * mean) / (cnt - 1.0);             // torch.std_mean: unbiased  (cnt 1: 0 / 0)
+    var = var < 0.0 ? 0.0 : var;                                           // (a NaN passes)
+    if (!(sh[1][0] < (double)INFINITY)) mean = (double)NAN;                // (fp32 squares cannot overflow a double: a non-finite sample)
     float meanf = (float)mean, stdf = (float)sqrt(var);
-    float den = fmaxf(stdf, 1e-5f);
+    float den = stdf < 1e-5f ? 1e-5f : stdf;                               // torch.clamp_min: NaN stays NaN
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         mean_std[0] = meanf;
         mean_std[1] = stdf;
     }
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         float a = ((ret[i] - vals[i]) - meanf) / den;
-        out[i] = fminf(fmaxf(a, -clip), clip);
+        out[i] = a < -clip ? -clip : (a > clip ? clip : a);              // torch.clamp: NaN stays NaN
     }
 }
 

@@ -21,7 +21,20 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Non-finite values surface where the reference's torch code surfaces them.  torch.clamp / clamp_min / clamp_max /
+// minimum return NaN for a NaN operand; fminf / fmaxf return the other operand.  On finite input these give the bits of
+// fminf(fmaxf(v, lo), hi), fminf(a, b), ...; a NaN falls through every compare and comes out.
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ float clamp_min_nan(float v, float lo) { return v < lo ? lo : v; }
+__device__ __forceinline__ float clamp_max_nan(float v, float hi) { return v > hi ? hi : v; }
+__device__ __forceinline__ float minimum_nan(float a, float b) { return a <= b ? a : (b < a ? b : __builtin_nanf("")); }
+// clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max = 1); a NaN norm gives a NaN coefficient, which reaches every element
+__device__ __forceinline__ float clip_coef(float max_norm, float norm) { return clamp_max_nan(max_norm / (norm + 1e-6f), 1.0f); }
+
 // pass 1: one thread per sample.  Unscaled gradients (the 1/cnt and gate factors are only known after the reduction).
+// The reference SELECTS the random-action rows before it evaluates them (ppo_agent.py:286-290): a row with mask != 1 adds exactly 0 to
+// every sum and gets a zero g_mean row whatever it holds (sel ? x : 0 - a product with m = 0 would turn its NaN / Inf into NaN), and a
+// NaN in a selected row reaches actor_loss as it does through torch.clamp and torch.minimum.
 __global__ __launch_bounds__(PPO_THREADS) void ppo_sample_kernel(int B, int A, const float *__restrict__ mean, const float *__restrict__ logstd,
                                                                  const float *__restrict__ norm_a, const float *__restrict__ old_logp,
                                                                  const float *__restrict__ adv, const float *__restrict__ mask,
@@ -40,14 +53,15 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_sample_kernel(int B, int A, c
     // (a_stride / s_stride: row stride of norm_a and element stride of the four per-sample scalars; A and 1 for separate dense arrays,
     //  the record width for the packed layout of parc_ppo_loss_packed)
     const size_t si = (size_t)ii * s_stride;
-    const float m = live ? (mask[si] == 1.0f ? 1.f : 0.f) : 0.f;
+    const bool sel = live && mask[si] == 1.0f;
+    const float m = sel ? 1.f : 0.f;
     const float *mu = mean + (size_t)ii * A, *ac = norm_a + (size_t)ii * a_stride;
     float zz = 0.f, viol = 0.f, reg = 0.f;
     for (int j = 0; j < A; ++j) {
         float mj = mu[j];
         float z = (ac[j] - mj) * s_istd[j];
         zz = fmaf(z, z, zz);
-        float vmin = fminf(mj + 1.0f, 0.f), vmax = fmaxf(mj - 1.0f, 0.f);
+        float vmin = clamp_max_nan(mj + 1.0f, 0.f), vmax = clamp_min_nan(mj - 1.0f, 0.f);
         viol += vmin * vmin + vmax * vmax;
         reg = fmaf(mj, mj, reg);
     }
@@ -55,12 +69,12 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_sample_kernel(int B, int A, c
     const float ratio = __expf(logp - old_logp[si]);
     const float ad = adv[si];
     const float lo = 1.0f - cfg.clip_ratio, hi = 1.0f + cfg.clip_ratio;
-    const float rc = fminf(fmaxf(ratio, lo), hi);
+    const float rc = clamp_nan(ratio, lo, hi);
     const float l0 = ad * ratio, l1 = ad * rc;
-    const float surr = fminf(l0, l1);
+    const float surr = minimum_nan(l0, l1);
     // d surr / d ratio: torch.minimum sends the gradient to l0 when l0 <= l1, else to l1, whose clamp passes it inside [lo, hi]
     const float dsurr = (l0 <= l1) ? ad : ((ratio >= lo && ratio <= hi) ? ad : 0.f);
-    const float c = -m * dsurr * ratio;                       // d(-sum m surr)/d logp_i   (x 1/cnt later)
+    const float c = sel ? -m * dsurr * ratio : 0.f;           // d(-sum m surr)/d logp_i   (x 1/cnt later)
     const float diff = tar_val[si] - pred[ii];
     if (live) {
         g_pred[i] = cfg.critic_l1 ? (diff > 0.f ? -1.f : (diff < 0.f ? 1.f : 0.f)) : -2.0f * diff;
@@ -68,19 +82,19 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_sample_kernel(int B, int A, c
         for (int j = 0; j < A; ++j) {
             float mj = mu[j];
             float z = (ac[j] - mj) * s_istd[j];
-            float vmin = fminf(mj + 1.0f, 0.f), vmax = fmaxf(mj - 1.0f, 0.f);
-            gm[j] = c * z * s_istd[j] + m * (cfg.bound_w * 2.0f * (vmin + vmax) + cfg.reg_w * 2.0f * mj);
+            float vmin = clamp_max_nan(mj + 1.0f, 0.f), vmax = clamp_min_nan(mj - 1.0f, 0.f);
+            gm[j] = sel ? c * z * s_istd[j] + m * (cfg.bound_w * 2.0f * (vmin + vmax) + cfg.reg_w * 2.0f * mj) : 0.f;
         }
     }
     // block partials, fixed order: lanes -> waves -> block
     float sc[PPO_NSCAL];
     sc[0] = m;
     sc[1] = live ? (cfg.critic_l1 ? fabsf(diff) : diff * diff) : 0.f;
-    sc[2] = m * surr;
-    sc[3] = m * (fabsf(ratio - 1.0f) > cfg.clip_ratio ? 1.f : 0.f);
-    sc[4] = m * ratio;
-    sc[5] = m * viol;
-    sc[6] = m * reg;
+    sc[2] = sel ? m * surr : 0.f;
+    sc[3] = m * (fabsf(ratio - 1.0f) > cfg.clip_ratio ? 1.f : 0.f);      // (a NaN ratio counts as unclipped, as in torch)
+    sc[4] = sel ? m * ratio : 0.f;
+    sc[5] = sel ? m * viol : 0.f;
+    sc[6] = sel ? m * reg : 0.f;
     sc[7] = 0.f;
     const int wv = tid >> 6, ln = tid & 63;
 #pragma unroll
@@ -90,7 +104,7 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_sample_kernel(int B, int A, c
     }
     for (int j = 0; j < A; ++j) {
         float z = live ? (ac[j] - mu[j]) * s_istd[j] : 0.f;
-        float v = wave_sum(c * (z * z - 1.0f));               // d logp / d logstd_j = z^2 - 1
+        float v = wave_sum(sel ? c * (z * z - 1.0f) : 0.f);   // d logp / d logstd_j = z^2 - 1
         if (ln == 0) s_part[wv][PPO_NSCAL + j] = v;
     }
     __syncthreads();
@@ -131,11 +145,12 @@ __global__ __launch_bounds__(256) void ppo_sample32_kernel(int B, int A, const f
         const bool live = i < B;
         const int ii = live ? i : 0;
         const size_t si = (size_t)ii * s_stride;
-        const float m = live ? (mask[si] == 1.0f ? 1.f : 0.f) : 0.f;
+        const bool sel = live && mask[si] == 1.0f;
+        const float m = sel ? 1.f : 0.f;
         const float mj = vj ? mean[(size_t)ii * A + j] : 0.f;
         const float aj = vj ? norm_a[(size_t)ii * a_stride + j] : 0.f;
         const float z = (aj - mj) * istd;
-        const float vmin = fminf(mj + 1.0f, 0.f), vmax = fmaxf(mj - 1.0f, 0.f);
+        const float vmin = clamp_max_nan(mj + 1.0f, 0.f), vmax = clamp_min_nan(mj - 1.0f, 0.f);
         float zz = vj ? z * z : 0.f, viol = vj ? vmin * vmin + vmax * vmax : 0.f, reg = vj ? mj * mj : 0.f;
 #pragma unroll
         for (int o = 16; o >= 1; o >>= 1) {
@@ -146,25 +161,25 @@ __global__ __launch_bounds__(256) void ppo_sample32_kernel(int B, int A, const f
         const float logp = -0.5f * zz + (-0.5f * (float)A * 1.8378770664093453f - sum_logstd);
         const float ratio = __expf(logp - old_logp[si]);
         const float ad = adv[si];
-        const float rc = fminf(fmaxf(ratio, lo), hi);
+        const float rc = clamp_nan(ratio, lo, hi);
         const float l0 = ad * ratio, l1 = ad * rc;
-        const float surr = fminf(l0, l1);
+        const float surr = minimum_nan(l0, l1);
         const float dsurr = (l0 <= l1) ? ad : ((ratio >= lo && ratio <= hi) ? ad : 0.f);
-        const float c = -m * dsurr * ratio;
+        const float c = sel ? -m * dsurr * ratio : 0.f;
         const float diff = tar_val[si] - pred[ii];
         if (live) {
             if (j == 0) g_pred[i] = cfg.critic_l1 ? (diff > 0.f ? -1.f : (diff < 0.f ? 1.f : 0.f)) : -2.0f * diff;
-            if (vj) g_mean[(size_t)i * A + j] = c * z * istd + m * (cfg.bound_w * 2.0f * (vmin + vmax) + cfg.reg_w * 2.0f * mj);
+            if (vj) g_mean[(size_t)i * A + j] = sel ? c * z * istd + m * (cfg.bound_w * 2.0f * (vmin + vmax) + cfg.reg_w * 2.0f * mj) : 0.f;
         }
         // (every lane of the group holds the same scalars; lane 0's copy is the one that is kept)
         acc[0] += m;
         acc[1] += live ? (cfg.critic_l1 ? fabsf(diff) : diff * diff) : 0.f;
-        acc[2] += m * surr;
+        acc[2] += sel ? m * surr : 0.f;
         acc[3] += m * (fabsf(ratio - 1.0f) > cfg.clip_ratio ? 1.f : 0.f);
-        acc[4] += m * ratio;
-        acc[5] += m * viol;
-        acc[6] += m * reg;
-        acc_ls += (live && vj) ? c * (z * z - 1.0f) : 0.f;
+        acc[4] += sel ? m * ratio : 0.f;
+        acc[5] += sel ? m * viol : 0.f;
+        acc[6] += sel ? m * reg : 0.f;
+        acc_ls += (sel && vj) ? c * (z * z - 1.0f) : 0.f;
     }
     if (j == 0) {
 #pragma unroll
@@ -517,9 +532,10 @@ extern "C" int parc_return_tracker_update(void *stream, int n_envs, int K, const
 // =============================================================================================
 // Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_ as MPOptimizer applies it to its flat gradient buffer):
 // x *= min(max_norm / (norm + 1e-6), 1) with norm read from device memory - one launch instead of add, reciprocal, mul, clamp, mul.
+// A NaN norm scales every element by NaN, as torch's clamp of the coefficient does.
 // =============================================================================================
 __global__ __launch_bounds__(256) void scale_by_clipped_norm_kernel(size_t n, float *x, const float *__restrict__ norm, float max_norm) {
-    const float s = fminf(max_norm / (norm[0] + 1e-6f), 1.0f);
+    const float s = clip_coef(max_norm, norm[0]);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) x[i] *= s;
 }
 
@@ -538,7 +554,9 @@ extern "C" int parc_scale_by_clipped_norm(void *stream, int64_t n, float *x, con
 // TWO passes over the 10.6 M parameters instead of four (norm, scale, multi-tensor SGD, + a zero fill): pass 1 the squared norm of
 // the flat gradient (1024 block partials), pass 2 every block first adds the partials in block order (fixed order, the same value
 // in every block), coef = min(max_norm / (norm + 1e-6), 1), then for its elements g' = coef g (+ wd p), m = mu m + g', p -= lr m
-// (torch.optim.SGD, dampening 0, no Nesterov; a zero momentum buffer reproduces its first-step rule buf = g').
+// (torch.optim.SGD, dampening 0, no Nesterov; a zero momentum buffer reproduces its first-step rule buf = g').  A NaN in the gradient
+// makes the norm and with it coef NaN: every parameter and momentum element becomes NaN, as after clip_grad_norm_ (max_norm <= 0: no
+// norm, the NaN stays in its element).
 // =============================================================================================
 #define SGD_PARTS 1024
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(size_t n4, const float4 *__restrict__ g, size_t n, const float *__restrict__ gs,
@@ -576,7 +594,7 @@ __global__ __launch_bounds__(256) void sgd_momentum_clip_kernel(size_t n, float 
             __syncthreads();
         }
         const float norm = sqrtf(s_red[0]);
-        coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+        coef = clip_coef(max_norm, norm);
         if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
     }
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -647,7 +665,7 @@ __global__ __launch_bounds__(256) void adamw_clip_kernel(size_t n, size_t n4, fl
             __syncthreads();
         }
         const float norm = sqrtf(s_red[0]);
-        coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+        coef = clip_coef(max_norm, norm);
         if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
     }
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
@@ -715,7 +733,8 @@ extern "C" int parc_adamw_step(void *stream, int64_t n, float *params, const flo
 
 // =============================================================================================
 // K12 observation normalisation: Normalizer.normalize (learning/normalizer.py:60-63)  out = clamp((x - mean) / std, -clip, clip)
-// in one pass (torch: subtract, divide, clamp = three passes).  Same fp32 operations, so the result is bit-identical.
+// in one pass (torch: subtract, divide, clamp = three passes).  Same fp32 operations: finite results are bit-identical, and a NaN (a NaN
+// observation, mean or std, 0 / 0 under a zero std) comes out as NaN, as from torch.clamp; +-inf clamps to +-clip.
 // =============================================================================================
 __global__ __launch_bounds__(256) void normalize_clamp_kernel(size_t n4, int dim4, const float4 *__restrict__ x, const float4 *__restrict__ mean,
                                                               const float4 *__restrict__ stdv, float clip, float4 *__restrict__ out) {
@@ -723,10 +742,10 @@ __global__ __launch_bounds__(256) void normalize_clamp_kernel(size_t n4, int dim
         const int c = (int)(i % (size_t)dim4);
         const float4 v = x[i], m = mean[c], s = stdv[c];
         float4 o;
-        o.x = fminf(fmaxf((v.x - m.x) / s.x, -clip), clip);
-        o.y = fminf(fmaxf((v.y - m.y) / s.y, -clip), clip);
-        o.z = fminf(fmaxf((v.z - m.z) / s.z, -clip), clip);
-        o.w = fminf(fmaxf((v.w - m.w) / s.w, -clip), clip);
+        o.x = clamp_nan((v.x - m.x) / s.x, -clip, clip);
+        o.y = clamp_nan((v.y - m.y) / s.y, -clip, clip);
+        o.z = clamp_nan((v.z - m.z) / s.z, -clip, clip);
+        o.w = clamp_nan((v.w - m.w) / s.w, -clip, clip);
         out[i] = o;
     }
 }
@@ -777,7 +796,7 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(int rows, int dim4
 }
 
 // The rollout step's three passes over the observation rows in ONE (parc_obs_ingest): Normalizer.normalize for the policy forward
-// (normalizer.py:60-63; same fp32 operations as normalize_clamp_kernel: bit-identical), ExperienceBuffer.record of the raw rows
+// (normalizer.py:60-63; same fp32 operations as normalize_clamp_kernel: bit-identical, NaN for NaN), ExperienceBuffer.record of the raw rows
 // (experience_buffer.py:55-59) into time row *copy_row, and stage 1 of Normalizer.record (the kernel above: same mapping, same
 // summation order, hence the same partial rows).  The rows are read once instead of three times.
 __global__ __launch_bounds__(256) void obs_ingest_kernel(int rows, int dim4, const float4 *__restrict__ x, const float4 *__restrict__ mean,
@@ -795,10 +814,10 @@ __global__ __launch_bounds__(256) void obs_ingest_kernel(int rows, int dim4, con
             const size_t i = (size_t)r * dim4 + c;
             const float4 v = x[i];
             float4 o;
-            o.x = fminf(fmaxf((v.x - m.x) / sd.x, -clip), clip);
-            o.y = fminf(fmaxf((v.y - m.y) / sd.y, -clip), clip);
-            o.z = fminf(fmaxf((v.z - m.z) / sd.z, -clip), clip);
-            o.w = fminf(fmaxf((v.w - m.w) / sd.w, -clip), clip);
+            o.x = clamp_nan((v.x - m.x) / sd.x, -clip, clip);
+            o.y = clamp_nan((v.y - m.y) / sd.y, -clip, clip);
+            o.z = clamp_nan((v.z - m.z) / sd.z, -clip, clip);
+            o.w = clamp_nan((v.w - m.w) / sd.w, -clip, clip);
             norm_out[i] = o;
             if (dst) {                       // (the buffer row is not read again before the update phase: streamed store)
                 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -876,7 +895,8 @@ extern "C" int parc_moments_accumulate(void *stream, int64_t rows, int dim, cons
 }
 
 // =============================================================================================
-// Backward of y = relu(x W^T + b) between the two GEMMs: g = gy * (y > 0), written over gy, and the bias gradient db = column sums
+// Backward of y = relu(x W^T + b) between the two GEMMs: g = y <= 0 ? 0 : gy (threshold_backward: a NaN activation passes gy), written
+// over gy, and the bias gradient db = column sums
 // of g, in ONE pass over the [rows, dim] activations (autograd runs threshold_backward, then a separate reduction that re-reads g,
 // then an accumulate into .grad).  256 columns x RB_ROWS rows per workgroup, float4 lanes, the 4 waves take rows round-robin and fold
 // their column sums through LDS; stage 2 adds the per-chunk partial rows in chunk order (fixed summation order, no atomics) and
@@ -896,7 +916,7 @@ __global__ __launch_bounds__(256) void relu_bwd_bias_partial_kernel(int rows, in
             const size_t i = (size_t)r * dim4 + c;
             float4 g = gy[i];
             const float4 a = y[i];
-            g.x = a.x > 0.f ? g.x : 0.f; g.y = a.y > 0.f ? g.y : 0.f; g.z = a.z > 0.f ? g.z : 0.f; g.w = a.w > 0.f ? g.w : 0.f;
+            g.x = a.x <= 0.f ? 0.f : g.x; g.y = a.y <= 0.f ? 0.f : g.y; g.z = a.z <= 0.f ? 0.f : g.z; g.w = a.w <= 0.f ? 0.f : g.w;
             gy[i] = g;
             s.x += g.x; s.y += g.y; s.z += g.z; s.w += g.w;
         }
