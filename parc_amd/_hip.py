@@ -14,7 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libparc_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip", "parc_moopt.hip"]
+SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip", "parc_moopt.hip",
+           "parc_augment.hip"]
 # The diagnostics library (tools/parc_diag.py; never loaded by this package): the same sources with -DPARC_DIAG_BUILD (timing-ablation bits of
 # parc_track_post_step, the heightmap kernel's measurement knobs) plus the one-env-per-lane reference formulation of the simulator.
 DIAG_LIB_PATH = os.path.join(LIB_DIR, "libparc_hip_diag.so")
@@ -106,7 +107,9 @@ _lib = None
 # same source; GVN scalar PRE on the unrolled 3x3 helpers).  The product's simulator kernels (parc_sim.hip) are correct at
 # every level (profiles/r02_sim_o3_bisect.txt) and are built at whichever measured faster: -O3 WITHOUT the SLP vectoriser since round 4
 # (its v_pk_* pairs come with a third more register moves: 114.9 -> 100.8 us per 4096-env step, profiles/r04_sim_step_variants.txt).
-OPT_LEVEL = {"parc_kin.hip": os.environ.get("PARC_KIN_OPT", "-O3 -fno-slp-vectorize"), "parc_sim.hip": os.environ.get("PARC_SIM_OPT", "-O3 -fno-slp-vectorize"), "parc_sim_ref.hip": "-O2"}
+OPT_LEVEL = {"parc_kin.hip": os.environ.get("PARC_KIN_OPT", "-O3 -fno-slp-vectorize"), "parc_sim.hip": os.environ.get("PARC_SIM_OPT", "-O3 -fno-slp-vectorize"), "parc_sim_ref.hip": "-O2",
+             # the augmentation restates separately rounded torch operations: no fused multiply-adds (parc_augment_core.h)
+             "parc_augment.hip": "-O3 -ffp-contract=off"}
 
 
 DIGEST_PATH = os.path.join(LIB_DIR, "libparc_hip.digest")
@@ -278,6 +281,9 @@ def _declare(L):
     if hasattr(L, "parc_moopt_abi"):
         from . import _hip_moopt
         _hip_moopt.declare(L)
+    if hasattr(L, "parc_augment_abi"):
+        from . import _hip_augment
+        _hip_augment.declare(L)
 
 
 EXPORTED = ["parc_abi_version", "parc_refresh_ray_obs_hfs", "parc_refresh_obs_hfs", "parc_dof_to_rot", "parc_rot_to_dof",
@@ -291,7 +297,8 @@ EXPORTED = ["parc_abi_version", "parc_refresh_ray_obs_hfs", "parc_refresh_obs_hf
             "parc_render", "parc_render_abi", "parc_motion_score", "parc_score_abi",
             "parc_netstats_workspace_floats", "parc_netstats_update", "parc_netstats_abs_colsum", "parc_netstats_dormant_count", "parc_netstats_abi",
             "parc_points_hf_sdf_ragged", "parc_points_hf_sdf_ragged_grad", "parc_temporal_terms_seg", "parc_temporal_terms_seg_grad",
-            "parc_segment_sums", "parc_moopt_abi"]
+            "parc_segment_sums", "parc_moopt_abi",
+            "parc_augment_frames", "parc_augment_terrains", "parc_augment_localize", "parc_augment_abi"]
 
 
 def check(rc, what):

@@ -566,7 +566,8 @@ class _BatchProblem(_ProblemTables):
             self.pair_contact = torch.where(last[:, None], torch.zeros_like(pc), pc).contiguous()
         self.src = (s_rp, s_rq, s_jr, s_bv, s_brv)
         # the descent's queries use the base_z of the single path (-10.0) for every terrain
-        self.table = terrain_util.HfTable(terrains, base_z=-10.0, device=dev)
+        # (a prepared table - the dataset augmentation writes the heights into its pool on the device - is taken as it is)
+        self.table = terrains if isinstance(terrains, terrain_util.HfTable) else terrain_util.HfTable(terrains, base_z=-10.0, device=dev)
         sph_seg, box_seg = self._build_tables(char_model, body_points, body_constraints, self.lengths, dev)
         self.sph_seg, self.box_seg = i32(sph_seg), i32(box_seg)
         self._cot = {}
@@ -665,6 +666,7 @@ def motion_contact_optimization_batch(src_frames, contacts, body_points, terrain
                                       loss_trace=None):
     """motion_contact_optimization for M motions, each on its own terrain, in ONE descent: src_frames, contacts, terrains,
     body_constraints (or None, or with None entries), exp_names and log_files are lists of length M; returns a list of [T_m, 34].
+    terrains may also be a terrain_util.HfTable of M entries whose heights already lie on the device (the dataset augmentation).
     One Adam over the three packed parameter tensors; one iteration is captured and replayed as in the single path, and its number of
     launches does not depend on M.  Every 25 iterations each motion's total and nine terms go to that motion's own log.
     loss_trace: optional list that receives ONE [num_iters, M] device tensor of per-motion totals."""

@@ -7,6 +7,7 @@ same field names -- motion pickles embed instances of it, so it must unpickle un
 """
 import contextlib
 import copy
+import ctypes
 import pickle
 import sys
 
@@ -94,6 +95,9 @@ class SubTerrain:
 
     def get_inbounds_grid_index(self, grid_ind):
         return torch.clamp(grid_ind, torch.zeros_like(self.dims), self.dims - 1)
+
+    def round_point_to_grid_point(self, point):
+        return torch.round((point - self.min_point) / self.dxdy) * self.dxdy + self.min_point
 
     def round_point_to_grid_index(self, point):
         return torch.round((point - self.min_point) / self.dxdy).to(dtype=torch.int64)
@@ -186,6 +190,37 @@ def get_local_hf_from_terrain(xy_points, terrain):
     the HIP kernel parc_refresh_obs_hfs instead)."""
     g = terrain.get_grid_index(xy_points)
     return terrain.hf[g[..., 0], g[..., 1]]
+
+
+def add_boxes_to_hf_at_xy_points(box_centers, hf, min_h, max_h, min_len, max_len, min_angle, max_angle):
+    """Stamp one random rotated box per row of box_centers [n, 2] (grid-index coordinates) into hf [X, Y], in place (reference
+    util/terrain_util.py:930-969).  Per box, in the reference's order: the two side lengths from torch.rand(2), the angle and then the
+    height from Python's random.  A cell belongs to a box when its index, turned about the centre by the angle, lies strictly inside
+    centre +- length / 2; a later box overwrites an earlier one.  The draws come from the host generators; on a GPU tensor all boxes
+    are stamped by one launch (parc_augment_terrains), on a CPU tensor by torch ops."""
+    import random
+    n = int(box_centers.shape[0])
+    lens, angles, hs = [], [], []
+    for _ in range(n):
+        lens.append(torch.rand(size=(2,), dtype=torch.float32) * (max_len - min_len) + min_len)
+        angles.append(random.random() * (max_angle - min_angle) + min_angle)
+        hs.append(random.random() * (max_h - min_h) + min_h)
+    if n == 0:
+        return
+    if hf.is_cuda:
+        from ..tools.motion_opt import augment_motions
+        augment_motions.stamp_boxes(hf, box_centers, torch.stack(lens), angles, hs)
+        return
+    X, Y = int(hf.shape[0]), int(hf.shape[1])
+    ii, jj = torch.meshgrid(torch.arange(X, dtype=torch.int64), torch.arange(Y, dtype=torch.int64), indexing="ij")
+    ij = torch.stack([ii, jj], dim=-1).to(torch.float32)
+    for b in range(n):
+        c = box_centers[b].to(torch.float32)
+        turned = torch_util.rotate_2d_vec(ij - c, angles[b] * torch.ones_like(ij[..., 0])) + c
+        half = lens[b] / 2
+        inside = (turned[..., 0] < c[0] + half[0]) & (turned[..., 0] > c[0] - half[0]) & (turned[..., 1] < c[1] + half[1]) & \
+            (turned[..., 1] > c[1] - half[1])
+        hf[ii, jj] = torch.where(inside, torch.ones_like(hf) * hs[b], hf[ii, jj])
 
 
 def slice_terrain_around_motion(motion_frames, terrain, padding=1.0):
@@ -437,6 +472,25 @@ class HfTable:
         raw = np.frombuffer(bytes(entries), dtype=np.uint8).copy()
         self.table = torch.from_numpy(raw).to(dev).contiguous()
         self.device = torch.device(dev)
+
+    @classmethod
+    def from_pool(cls, pool, table, shapes, base_z=-10.0):
+        """A table whose heights already lie in a device pool (the dataset augmentation writes them there): `table` is the device byte
+        tensor of len(shapes) parc_moopt_terrain_t rows over `pool`.  Nothing is copied or read back."""
+        from .. import _hip_moopt
+        self = cls.__new__(cls)
+        n = len(shapes)
+        assert table.dtype == torch.uint8 and table.is_contiguous() and table.numel() == n * ctypes.sizeof(_hip_moopt.MooptTerrainS)
+        assert pool.dtype == torch.float32 and pool.is_contiguous() and pool.device == table.device
+        self.shapes = [(int(x), int(y)) for x, y in shapes]
+        self.num_terrains = n
+        self.base_z = [float(base_z)] * n
+        self.entries = None
+        self.pool, self.table, self.device = pool, table, pool.device
+        return self
+
+    def __len__(self):
+        return self.num_terrains
 
 
 def points_hf_sdf_ragged(points, row_terrain, table, inverted=True, radius=None):
