@@ -15,7 +15,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libparc_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip", "parc_moopt.hip",
-           "parc_augment.hip"]
+           "parc_augment.hip", "parc_hfgather.hip", "parc_motion.hip", "parc_pose_opt.hip", "parc_returns.hip"]
 # The diagnostics library (tools/parc_diag.py; never loaded by this package): the same sources with -DPARC_DIAG_BUILD (timing-ablation bits of
 # parc_track_post_step, the heightmap kernel's measurement knobs) plus the one-env-per-lane reference formulation of the simulator.
 DIAG_LIB_PATH = os.path.join(LIB_DIR, "libparc_hip_diag.so")
@@ -107,7 +107,10 @@ _lib = None
 # same source; GVN scalar PRE on the unrolled 3x3 helpers).  The product's simulator kernels (parc_sim.hip) are correct at
 # every level (profiles/r02_sim_o3_bisect.txt) and are built at whichever measured faster: -O3 WITHOUT the SLP vectoriser since round 4
 # (its v_pk_* pairs come with a third more register moves: 114.9 -> 100.8 us per 4096-env step, profiles/r04_sim_step_variants.txt).
-OPT_LEVEL = {"parc_kin.hip": os.environ.get("PARC_KIN_OPT", "-O3 -fno-slp-vectorize"), "parc_sim.hip": os.environ.get("PARC_SIM_OPT", "-O3 -fno-slp-vectorize"), "parc_sim_ref.hip": "-O2",
+NO_SLP = "-O3 -fno-slp-vectorize"
+OPT_LEVEL = {"parc_kin.hip": os.environ.get("PARC_KIN_OPT", NO_SLP), "parc_sim.hip": os.environ.get("PARC_SIM_OPT", NO_SLP), "parc_sim_ref.hip": "-O2",
+             # measured under the flags of parc_kin.hip; plain -O3 gives most of their kernels other code ("Source files")
+             "parc_hfgather.hip": NO_SLP, "parc_motion.hip": NO_SLP, "parc_pose_opt.hip": NO_SLP, "parc_returns.hip": NO_SLP,
              # the augmentation restates separately rounded torch operations: no fused multiply-adds (parc_augment_core.h)
              "parc_augment.hip": "-O3 -ffp-contract=off"}
 

@@ -4,7 +4,7 @@ Host-side mirror of the reference's ``anim/kin_char_model.py`` (KinCharModel :14
 same constructor, method names and attribute names (``_body_names``, ``_parent_indices``,
 ``_local_translation``, ``_local_rotation``, ``_joints``, ``_lower_dof_limits`` ...), because the env,
 agent and recorder reach into them.  The batch math (dof_to_rot / rot_to_dof / forward_kinematics,
-reference :478-541) runs in the HIP kernels of parc_amd/csrc/parc_kin.hip; there is no CPU fallback.
+reference :478-541) runs in the HIP kernels of parc_amd/csrc/parc_motion.hip; there is no CPU fallback.
 
 The parser additionally keeps what the simulator needs from the MJCF and the reference only hands to
 Isaac Gym: geoms with densities, joint stiffness / damping / armature, motor gears.

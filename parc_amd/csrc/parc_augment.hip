@@ -6,14 +6,9 @@
 
 #include "../../include/parc_augment.h"
 #include "parc_augment_core.h"
+#include "parc_launch.h"
 
 using namespace parc_aug;
-
-#define AUG_CHECK_LAUNCH()                          \
-    do {                                            \
-        hipError_t _e = hipGetLastError();          \
-        if (_e != hipSuccess) return (int)_e;       \
-    } while (0)
 
 #define AUG_CELL_THREADS 256
 
@@ -74,7 +69,7 @@ extern "C" int parc_augment_frames(void *stream, int n_variants, int n_src_rows,
     if (rc != PARC_OK) return rc == PARC_AUG_NOTHING ? PARC_OK : rc;
     hipLaunchKernelGGL(augment_frames_kernel, dim3((unsigned)n_variants), dim3(PARC_AUG_THREADS), 0, (hipStream_t)stream, n_src_rows, contact_width,
                        src_frames, src_contacts, vars, n_out_rows, out_frames, out_contacts, bounds);
-    AUG_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 
@@ -92,7 +87,7 @@ extern "C" int parc_augment_terrains(void *stream, int n_variants, int64_t n_cel
     hipLaunchKernelGGL(augment_terrains_kernel, dim3((unsigned)nb), dim3(AUG_CELL_THREADS), 0, (hipStream_t)stream, n_variants, n_cells, cell_start, vars,
                        n_sources, src_table, src_pool, src_pool_floats, out_table, points, points_floats, boxes, n_boxes, frames, n_rows, out_pool,
                        out_pool_floats, canon);
-    AUG_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 
@@ -102,7 +97,7 @@ extern "C" int parc_augment_localize(void *stream, int n_variants, const parc_au
     if (rc != PARC_OK) return rc == PARC_AUG_NOTHING ? PARC_OK : rc;
     hipLaunchKernelGGL(augment_localize_kernel, dim3((unsigned)n_variants), dim3(PARC_AUG_THREADS), 0, (hipStream_t)stream, vars, canon, frames, n_rows,
                        (parc_moopt_terrain_t *)hf_table);
-    AUG_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 

@@ -1,5 +1,5 @@
-// Body-per-lane forward kinematics: a pose is handled by a 16-lane group, lane b = body b (b = 0 root).  Shared by the tracker kernels
-// (parc_kin.hip) and the motion scorer (parc_score.hip).  Device only.
+// Body-per-lane forward kinematics: a pose is handled by a 16-lane group, lane b = body b (b = 0 root).  Shared by the tracker step
+// (parc_kin.hip), the stand-alone kinematics (parc_motion.hip) and the motion scorer (parc_score.hip).  Device only.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,15 +1,27 @@
-// Kinematic / observation / reward / termination / TD(lambda) kernels of the PARC tracker hot path,
-// written for gfx950 (MI355X): 64-lane wavefronts, 16-lane body groups, LDS-staged observation rows.
-// C-ABI in include/parc_hip.h.  Reference citations are relative to the reference root.
+// The tracker step of the PARC hot path: the fused post-physics pass (observation, reward, termination), the reference state, the
+// observation gather of the other layouts, the device-side resets and the fail rates, written for gfx950 (MI355X): 64-lane wavefronts,
+// 16-lane body groups, LDS-staged observation rows.  The stand-alone heightmap gather is in parc_hfgather.hip, the motion library and
+// character-model kernels in parc_motion.hip, the motion optimiser's primitives in parc_pose_opt.hip, the learner's returns in
+// parc_returns.hip.  C-ABI in include/parc_hip.h.  Reference citations are relative to the reference root.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include "../../include/parc_hip.h"
+#include "parc_launch.h"
 #include "parc_math.h"
 #include "parc_math_pk.h"
-#include "parc_fk_group.h"     // GRP, shfl16, sum16, any16, fk_consts_of, group_fk
-#include "parc_moopt_core.h"   // tt_args, tt_forward_body, tt_backward_body
+#include "parc_fk_group.h"      // GRP, shfl16, sum16, any16, fk_consts_of, group_fk
+#include "parc_hf_lookup.h"     // hf_lookup, hf_env_params
+#include "parc_pose_lane.h"     // model_ok, joint_rot_to_dof
+#include "parc_motion_query.h"  // make_query, query_quat, lerp_ref, query_root_pos
+
+// the timing-ablation bits of track_post_kernel exist only in the diagnostics build (-DPARC_DIAG_BUILD)
+#ifdef PARC_DIAG_BUILD
+#define PARC_DIAG(...) __VA_ARGS__
+#else
+#define PARC_DIAG(...)
+#endif
 
 // 4 floats moved by one 16-byte instruction from / to an address that is only 4-byte aligned (global memory takes it)
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -22,314 +34,7 @@ typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 #define POST_STORE4(p, v) (*reinterpret_cast<f4u *>(p) = (v))
 #endif
 
-#define PARC_CHECK_LAUNCH()                         \
-    do {                                            \
-        hipError_t _e = hipGetLastError();          \
-        if (_e != hipSuccess) return (int)_e;       \
-    } while (0)
-
-// =============================================================================================
-// K5  local heightmap gather
-// =============================================================================================
-// One workgroup = HF_EPB consecutive envs; every thread owns one 16-byte output slot (4 ray points) whose
-// template coordinates stay in registers across those envs, so a wave stores 1 KiB contiguous per
-// instruction (the row's misaligned head/tail elements are slot 0 / the last slot).  The heightfield is
-// L1/L2-resident (a 441-point fan touches ~100 cells), so the kernel is bound by instruction issue, not
-// HBM: per env the lookup is folded into two affine maps in CELL units,
-//     u_i = x*(c/dx) - y*(s/dx) + (gx-min_x)/dx ,   u_j = x*(s/dy) + y*(c/dy) + (gy-min_y)/dy
-// (c,s = cos/sin of the heading taken directly from the rotated x axis: cos(atan2(b,a)) = a/|(a,b)|),
-// then rndne + clamp + one load per point.  This reassociates the reference's fp32 expression
-// (rotate, add root, subtract min, divide): values agree except for queries within a few ulp of a cell
-// boundary (tests bound this), the returned heights themselves are exact copies.
-#define HF_THREADS 128
-
-// util/terrain_util.py:107-126: torch.round (half to even) then clamp to the grid
-PARC_DEV float hf_lookup(const parc_terrain_t &t, float px, float py) {
-    float fi = rintf((px - t.min_x) / t.dx);
-    float fj = rintf((py - t.min_y) / t.dy);
-    fi = fminf(fmaxf(fi, 0.f), (float)(t.dim_x - 1));
-    fj = fminf(fmaxf(fj, 0.f), (float)(t.dim_y - 1));
-    return t.hf[(int)fi * t.dim_y + (int)fj];
-}
-
-struct hf_env_prm {
-    float ax, bx, cx, ay, by, cy, gz;
-};
-
-template <bool FROM_STATE>
-PARC_DEV hf_env_prm hf_env_params(int e, const float *__restrict__ root, const float *__restrict__ aux, const parc_terrain_t &ter,
-                                  float inv_dx, float inv_dy) {
-    float gx, gy, gz, c, s;
-    if (FROM_STATE) {
-        // ig_parkour_env.py:640-641: global xyz = root pos + env offset; heading of R(q) e_x (torch_util.py:470-479)
-        const float *rs = root + (size_t)e * 13;
-        gx = rs[0] + aux[3 * e + 0];
-        gy = rs[1] + aux[3 * e + 1];
-        gz = rs[2] + aux[3 * e + 2];
-        float qx = rs[3], qy = rs[4], qz = rs[5], qw = rs[6];
-        float a = 1.0f - 2.0f * (qy * qy + qz * qz);
-        float b = 2.0f * (qw * qz + qx * qy);
-        float n2 = a * a + b * b;
-        float inv = rsqrtf(n2);
-        c = n2 > 0.f ? a * inv : 1.0f;   // atan2(0,0) = 0
-        s = n2 > 0.f ? b * inv : 0.0f;
-    } else {
-        gx = root[3 * e + 0];
-        gy = root[3 * e + 1];
-        gz = root[3 * e + 2];
-        sincosf(aux[e], &s, &c);
-    }
-    hf_env_prm p;
-    p.ax = c * inv_dx;
-    p.bx = -s * inv_dx;
-    p.cx = (gx - ter.min_x) * inv_dx;
-    p.ay = s * inv_dy;
-    p.by = c * inv_dy;
-    p.cy = (gy - ter.min_y) * inv_dy;
-    p.gz = gz;
-    return p;
-}
-
-// HF_G: groups of HF_THREADS threads per workgroup, each group working on its own HF_EPB envs (fewer, fatter workgroups for the
-// same number of waves: at 4096 envs the launch is dispatch-bound)
-template <bool FROM_STATE, int HF_EPB, int ABL = 0, int HF_G = 1>
-__global__ __launch_bounds__(HF_THREADS *HF_G) void hf_gather_kernel(int n_envs, const float *__restrict__ ray_xy, int n_points,
-                                                                      const float *__restrict__ root, const float *__restrict__ aux,
-                                                                      parc_terrain_t ter, float min_h, float max_h,
-                                                                      float *__restrict__ out, int64_t out_stride, int head) {
-    const int tid = threadIdx.x % HF_THREADS;
-    const int e0 = (blockIdx.x * HF_G + threadIdx.x / HF_THREADS) * HF_EPB;
-    if (HF_G > 1 && e0 >= n_envs) return;
-    const float inv_dx = 1.0f / ter.dx, inv_dy = 1.0f / ter.dy;
-    const float max_i = (float)(ter.dim_x - 1), max_j = (float)(ter.dim_y - 1);
-    hf_env_prm prm[HF_EPB];
-    const unsigned out_bytes = (unsigned)min((unsigned long long)n_envs * (unsigned long long)out_stride * 4ull, 0xFFFFFFFFull);
-    __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(out, 0, out_bytes, 0x00020000);
-#pragma unroll
-    for (int ee = 0; ee < HF_EPB; ++ee) prm[ee] = hf_env_params<FROM_STATE>(min(e0 + ee, n_envs - 1), root, aux, ter, inv_dx, inv_dy);
-    // slot 0: the `head` leading scalars; slots 1..nbody: aligned float4s; last slot: trailing scalars
-    const int nbody = (n_points - head) >> 2;
-    const int tail = n_points - head - 4 * nbody;
-    const int nslots = nbody + 2;
-    for (int q = tid; q < nslots; q += HF_THREADS) {
-        int p0, cnt;
-        if (q == 0) {
-            p0 = 0;
-            cnt = head;
-        } else if (q <= nbody) {
-            p0 = head + 4 * (q - 1);
-            cnt = 4;
-        } else {
-            p0 = head + 4 * nbody;
-            cnt = tail;
-        }
-        if (cnt == 0) continue;
-        float rx[4], ry[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int p = min(p0 + i, n_points - 1);
-            rx[i] = ray_xy[2 * p];
-            ry[i] = ray_xy[2 * p + 1];
-        }
-        float h[HF_EPB][4];
-#pragma unroll
-        for (int ee = 0; ee < HF_EPB; ++ee) {
-            const hf_env_prm pr = prm[ee];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float ui = fmaf(rx[i], pr.ax, fmaf(ry[i], pr.bx, pr.cx));
-                float uj = fmaf(rx[i], pr.ay, fmaf(ry[i], pr.by, pr.cy));
-                ui = __builtin_amdgcn_fmed3f(rintf(ui), 0.f, max_i);
-                uj = __builtin_amdgcn_fmed3f(rintf(uj), 0.f, max_j);
-                float v = ((ABL == 1 || ABL == 5) ? (ui + uj) : ter.hf[(int)ui * ter.dim_y + (int)uj]) - pr.gz;
-                h[ee][i] = __builtin_amdgcn_fmed3f(v, min_h, max_h);
-            }
-        }
-#pragma unroll
-        for (int ee = 0; ee < HF_EPB; ++ee) {
-            int e = e0 + ee;
-            if (e >= n_envs) break;
-            const size_t off = (size_t)e * out_stride + p0;
-            float *o = out + off;
-            if (ABL == 2 || ABL == 5) {
-                if (h[ee][0] + h[ee][1] + h[ee][2] + h[ee][3] == 12345.678f) o[0] = 1.f;   // ablation: keep the math, drop the stores
-            } else if (cnt == 4) {
-                if (ABL == 3 || ABL == 4) {
-                    typedef float f32x4 __attribute__((ext_vector_type(4)));
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    f32x4 v = {h[ee][0], h[ee][1], h[ee][2], h[ee][3]};
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, (unsigned)(off * 4), 0, ABL == 3 ? 16 : 2);
-                } else {
-                    *reinterpret_cast<float4 *>(o) = make_float4(h[ee][0], h[ee][1], h[ee][2], h[ee][3]);
-                }
-            } else {
-                for (int i = 0; i < cnt; ++i) o[i] = h[ee][i];
-            }
-        }
-    }
-}
-
-// generic fallback (arbitrary row alignment): one thread per output value
-template <bool FROM_STATE>
-__global__ __launch_bounds__(256) void hf_gather_scalar_kernel(int n_envs, const float *__restrict__ ray_xy, int n_points,
-                                                               const float *__restrict__ root, const float *__restrict__ aux,
-                                                               parc_terrain_t ter, float min_h, float max_h,
-                                                               float *__restrict__ out, int64_t out_stride) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)n_envs * n_points) return;
-    int e = (int)(idx / n_points), p = (int)(idx % n_points);
-    float gx, gy, gz, hd;
-    if (FROM_STATE) {
-        const float *rs = root + (size_t)e * 13;
-        gx = rs[0] + aux[3 * e + 0];
-        gy = rs[1] + aux[3 * e + 1];
-        gz = rs[2] + aux[3 * e + 2];
-        hd = calc_heading(ld4(rs + 3));
-    } else {
-        gx = root[3 * e + 0];
-        gy = root[3 * e + 1];
-        gz = root[3 * e + 2];
-        hd = aux[e];
-    }
-    float c = cosf(hd), s = sinf(hd);
-    float x = ray_xy[2 * p], y = ray_xy[2 * p + 1];
-    float v = hf_lookup(ter, (x * c - y * s) + gx, (x * s + y * c) + gy) - gz;
-    out[(size_t)e * out_stride + p] = fminf(fmaxf(v, min_h), max_h);
-}
-
-// Measurement knobs of the standalone heightmap kernel exist only in the diagnostics build (-DPARC_DIAG_BUILD: tools/parc_diag.py builds
-// libparc_hip_diag.so, tools/parc_diag.h declares its extra entry points); the product library has them as constants and
-// exports no setter, so nothing a test or tool does can leave a later product launch on another kernel.
-#ifdef PARC_DIAG_BUILD
-static int g_hf_epb = 2;
-static int g_hf_groups = 1;   // 128-thread env groups per workgroup (1, 2, 4, 8)
-static int g_hf_abl = 0;      // timing-only ablations (outputs wrong): 1 no gather, 2 no stores, ...
-#define PARC_DIAG(...) __VA_ARGS__
-#else
-static constexpr int g_hf_epb = 2;
-#define PARC_DIAG(...)
-#endif
-
-static int launch_hf(bool from_state, void *stream, int n_envs, const float *ray_xy, int n_points, const float *root,
-                     const float *aux, parc_terrain_t ter, float min_h, float max_h, float *out, int64_t out_stride) {
-    if (n_envs < 0 || n_points <= 0 || !ray_xy || !root || !aux || !out || !ter.hf || out_stride < n_points) return PARC_EINVAL;
-    if (n_envs == 0) return PARC_OK;
-    int head;
-    if ((out_stride & 3) == 0) {
-        head = (int)(((16 - ((uintptr_t)out & 15)) & 15) >> 2);  // same misalignment on every row
-        if (head > n_points) head = n_points;
-    } else {
-        head = n_points;  // rows are differently aligned: all-scalar path through slot 0 (not vectorised)
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (head == n_points && n_points > 3) {
-        // rows are not uniformly 16-byte aligned: one thread per point, dword stores
-        long total = (long)n_envs * n_points;
-        dim3 g2((unsigned)((total + 255) / 256)), b2(256);
-        if (from_state)
-            hipLaunchKernelGGL(hf_gather_scalar_kernel<true>, g2, b2, 0, st, n_envs, ray_xy, n_points, root, aux, ter, min_h, max_h, out, out_stride);
-        else
-            hipLaunchKernelGGL(hf_gather_scalar_kernel<false>, g2, b2, 0, st, n_envs, ray_xy, n_points, root, aux, ter, min_h, max_h, out, out_stride);
-        PARC_CHECK_LAUNCH();
-        return PARC_OK;
-    }
-#define HF_LAUNCH3(FS, EPB, AB)                                                                                          \
-    hipLaunchKernelGGL((hf_gather_kernel<FS, EPB, AB>), dim3((n_envs + EPB - 1) / EPB), dim3(HF_THREADS), 0, st, n_envs, ray_xy, \
-                       n_points, root, aux, ter, min_h, max_h, out, out_stride, head)
-#define HF_LAUNCH(FS, EPB)                                                                                               \
-    hipLaunchKernelGGL((hf_gather_kernel<FS, EPB>), dim3((n_envs + EPB - 1) / EPB), dim3(HF_THREADS), 0, st, n_envs, ray_xy, \
-                       n_points, root, aux, ter, min_h, max_h, out, out_stride, head)
-    const int epb = g_hf_epb;
-#ifdef PARC_DIAG_BUILD
-#define HF_LAUNCH_G(AB, G)                                                                                                              \
-    hipLaunchKernelGGL((hf_gather_kernel<true, 2, AB, G>), dim3((n_envs + 2 * G - 1) / (2 * G)), dim3(HF_THREADS * G), 0, st, n_envs, ray_xy, \
-                       n_points, root, aux, ter, min_h, max_h, out, out_stride, head)
-    if (from_state && g_hf_groups > 1) {
-        const bool empty = g_hf_abl == 5;
-        if (g_hf_groups == 2) { if (empty) HF_LAUNCH_G(5, 2); else HF_LAUNCH_G(0, 2); }
-        else if (g_hf_groups == 4) { if (empty) HF_LAUNCH_G(5, 4); else HF_LAUNCH_G(0, 4); }
-        else { if (empty) HF_LAUNCH_G(5, 8); else HF_LAUNCH_G(0, 8); }
-        PARC_CHECK_LAUNCH();
-        return PARC_OK;
-    }
-#undef HF_LAUNCH_G
-    if (from_state && g_hf_abl == 1) HF_LAUNCH3(true, 2, 1);
-    else if (from_state && g_hf_abl == 2) HF_LAUNCH3(true, 2, 2);
-    else if (from_state && g_hf_abl == 3) HF_LAUNCH3(true, 2, 3);
-    else if (from_state && g_hf_abl == 4) HF_LAUNCH3(true, 2, 4);
-    else if (from_state && g_hf_abl == 5) HF_LAUNCH3(true, 2, 5);
-    else
-#endif
-    if (from_state) {
-        if (epb == 1) HF_LAUNCH(true, 1);
-        else if (epb == 4) HF_LAUNCH(true, 4);
-        else if (epb == 8) HF_LAUNCH(true, 8);
-        else HF_LAUNCH(true, 2);
-    } else {
-        if (epb == 1) HF_LAUNCH(false, 1);
-        else if (epb == 4) HF_LAUNCH(false, 4);
-        else if (epb == 8) HF_LAUNCH(false, 8);
-        else HF_LAUNCH(false, 2);
-    }
-#undef HF_LAUNCH
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-#ifdef PARC_DIAG_BUILD
-// tuning knob (envs per workgroup of the heightmap kernel: 1, 2, 4 or 8); not part of the stable ABI
-extern "C" int parc_tune_hf_groups(int g) {
-    if (g != 1 && g != 2 && g != 4 && g != 8) return PARC_EINVAL;
-    g_hf_groups = g;
-    return PARC_OK;
-}
-extern "C" int parc_tune_hf_ablation(int a) {
-    g_hf_abl = a;
-    return PARC_OK;
-}
-
-extern "C" int parc_tune_hf_envs_per_block(int epb) {
-    if (epb != 1 && epb != 2 && epb != 4 && epb != 8) return PARC_EINVAL;
-    g_hf_epb = epb;
-    return PARC_OK;
-}
-#endif
-
-extern "C" int parc_refresh_ray_obs_hfs(void *stream, int n_envs, const float *ray_xy, int n_points, const float *root_pos_xyz,
-                                        const float *heading, parc_terrain_t terrain, float min_h, float max_h, float *out,
-                                        int64_t out_stride) {
-    return launch_hf(false, stream, n_envs, ray_xy, n_points, root_pos_xyz, heading, terrain, min_h, max_h, out, out_stride);
-}
-
-extern "C" int parc_refresh_obs_hfs(void *stream, int n_envs, const float *ray_xy, int n_points, const float *root_state,
-                                    const float *env_offsets, parc_terrain_t terrain, float min_h, float max_h, float *out,
-                                    int64_t out_stride) {
-    return launch_hf(true, stream, n_envs, ray_xy, n_points, root_state, env_offsets, terrain, min_h, max_h, out, out_stride);
-}
-
-// =============================================================================================
-// Body-per-lane helpers: a pose is handled by a 16-lane group, lane b = body b (b = 0 root).
-// =============================================================================================
-
-static bool model_ok(const parc_char_model_t &m) { return m.num_bodies >= 1 && m.num_bodies <= PARC_MAX_BODIES && m.dof_size <= PARC_MAX_DOFS; }
-
-// anim/kin_char_model.py:57-77: one joint's dofs -> quaternion (lane b >= 1)
-template <bool LIB = false>
-PARC_DEV q4 joint_dof_to_rot(const parc_char_model_t &m, int b, const float *dof, int stride) {
-    int jt = m.joint_type[b];
-    if (jt == PARC_JOINT_HINGE) {
-        v3 ax = mk3(m.joint_axis[b][0], m.joint_axis[b][1], m.joint_axis[b][2]);
-        float an = dof[m.dof_idx[b] * stride];
-        return LIB ? axis_angle_to_quat_lib(ax, an) : axis_angle_to_quat(ax, an);
-    } else if (jt == PARC_JOINT_SPHERICAL) {
-        int d = m.dof_idx[b];
-        v3 em = mk3(dof[d * stride], dof[(d + 1) * stride], dof[(d + 2) * stride]);
-        return LIB ? exp_map_to_quat_lib(em) : exp_map_to_quat(em);
-    }
-    return mk4(0.f, 0.f, 0.f, 1.f);
-}
-
-// the same with the joint's constants already at hand (type, first dof, hinge axis)
+// joint_dof_to_rot (parc_pose_lane.h) with the joint's constants already at hand (type, first dof, hinge axis)
 // Both joint kinds end in axis_angle_to_quat (exp_map_to_quat of parc_math.h = the steps below, then that call): the lanes of a group
 // differ in kind, so each kind's branch only prepares (axis, angle) and the common tail is issued once instead of once per kind.
 PARC_DEV q4 joint_dof_to_rot(int jt, int d, v3 ax, const float *dof, int stride) {
@@ -352,32 +57,6 @@ PARC_DEV q4 joint_dof_to_rot(int jt, int d, v3 ax, const float *dof, int stride)
     return (jt == PARC_JOINT_HINGE || jt == PARC_JOINT_SPHERICAL) ? q : mk4(0.f, 0.f, 0.f, 1.f);
 }
 
-// anim/kin_char_model.py:79-100: one joint's quaternion -> dofs
-// (dof2, when given, receives the same values at stride 2: the position slots of an interleaved dof_state row)
-PARC_DEV void joint_rot_to_dof(const parc_char_model_t &m, int b, q4 q, float *dof, float *dof2 = nullptr) {
-    int jt = m.joint_type[b];
-    if (jt == PARC_JOINT_HINGE) {
-        v3 ax;
-        float an;
-        quat_to_axis_angle(q, ax, an);
-        float d = m.joint_axis[b][0] * ax.x + m.joint_axis[b][1] * ax.y + m.joint_axis[b][2] * ax.z;
-        if (d < 0.f) an *= -1.f;
-        dof[m.dof_idx[b]] = an;
-        if (dof2) dof2[2 * m.dof_idx[b]] = an;
-    } else if (jt == PARC_JOINT_SPHERICAL) {
-        v3 e = quat_to_exp_map(q);
-        int d = m.dof_idx[b];
-        dof[d] = e.x;
-        dof[d + 1] = e.y;
-        dof[d + 2] = e.z;
-        if (dof2) {
-            dof2[2 * d] = e.x;
-            dof2[2 * d + 2] = e.y;
-            dof2[2 * d + 4] = e.z;
-        }
-    }
-}
-
 // ---- the same on two poses per lane (parc_math_pk.h): the cross-lane moves are per component, the arithmetic is packed
 PARC_DEV f2 shfl16(f2 v, int src) { return f2{shfl16(v.x, src), shfl16(v.y, src)}; }
 PARC_DEV q4p shfl16(q4p q, int src) { return q4p{shfl16(q.x, src), shfl16(q.y, src), shfl16(q.z, src), shfl16(q.w, src)}; }
@@ -397,541 +76,6 @@ PARC_DEV void group_fk(const fk_consts &k, int max_depth, v3p root_pos, q4p root
             if (LEAF_ROT || lev < max_depth) rot = quat_mul(pr, lq);
         }
     }
-}
-
-struct frame_query {
-    const float *row0, *row1;
-    float blend, loop_phase;
-    int wrap, idx0, idx1;     // idx = absolute frame row
-};
-
-// anim/motion_lib.py:443-456,527-538 (+ :458-475 loop offset)
-PARC_DEV frame_query make_query(const parc_motion_lib_t &ml, int64_t id, float time) {
-    frame_query fq;
-    float len = ml.length[id];
-    fq.wrap = ml.loop_mode[id] == 1;
-    float phase = time / len;
-    fq.loop_phase = floorf(phase);
-    if (fq.wrap) phase = phase - floorf(phase);
-    phase = fminf(fmaxf(phase, 0.f), 1.f);
-    int nf = ml.num_frames[id];
-    float fp = phase * (float)(nf - 1);
-    int i0 = (int)fp;
-    int i1 = min(i0 + 1, nf - 1);
-    fq.blend = fp - (float)i0;
-    int st = ml.start_idx[id];
-    fq.idx0 = st + i0;
-    fq.idx1 = st + i1;
-    fq.row0 = ml.frames + (size_t)fq.idx0 * ml.row_stride;
-    fq.row1 = ml.frames + (size_t)fq.idx1 * ml.row_stride;
-    return fq;
-}
-
-// lane b: slerped quaternion b of the frame pair (b = 0 root rotation, b >= 1 joint b-1)
-PARC_DEV q4 query_quat(const frame_query &fq, int b) {
-    float4 a = *reinterpret_cast<const float4 *>(fq.row0 + 4 * b);
-    float4 c = *reinterpret_cast<const float4 *>(fq.row1 + 4 * b);
-    return slerp(mk4(a.x, a.y, a.z, a.w), mk4(c.x, c.y, c.z, c.w), fq.blend);
-}
-
-PARC_DEV float lerp_ref(float a, float b, float t) { return (1.0f - t) * a + t * b; }
-
-PARC_DEV v3 query_root_pos(const parc_motion_lib_t &ml, const frame_query &fq, int64_t id) {
-    const float *p0 = fq.row0 + ml.off_pos, *p1 = fq.row1 + ml.off_pos;
-    v3 p = mk3(lerp_ref(p0[0], p1[0], fq.blend), lerp_ref(p0[1], p1[1], fq.blend), lerp_ref(p0[2], p1[2], fq.blend));
-    if (fq.wrap) {
-        const float *d = ml.pos_delta + 3 * id;
-        p = p + mk3(fq.loop_phase * d[0], fq.loop_phase * d[1], fq.loop_phase * d[2]);
-    }
-    return p;
-}
-
-// =============================================================================================
-// K3 standalone (16 lanes per query, 4 queries per wave)
-// =============================================================================================
-__global__ __launch_bounds__(256) void motion_frame_kernel(parc_motion_lib_t ml, int nq, const int64_t *__restrict__ ids,
-                                                           const float *__restrict__ times, float *root_pos, float *root_rot,
-                                                           float *root_vel, float *root_ang_vel, float *joint_rot,
-                                                           float *dof_vel, float *contacts) {
-    int q = (blockIdx.x * blockDim.x + threadIdx.x) / GRP;
-    int b = threadIdx.x % GRP;
-    if (q >= nq) return;
-    const int B = ml.num_bodies, J = B - 1, D = ml.dof_size;
-    int64_t id = ids[q];
-    frame_query fq = make_query(ml, id, times[q]);
-    if (b < B) {
-        q4 r = query_quat(fq, b);
-        if (b == 0) st4(root_rot + 4 * (size_t)q, r);
-        else st4(joint_rot + ((size_t)q * J + (b - 1)) * 4, r);
-        contacts[(size_t)q * B + b] = lerp_ref(fq.row0[ml.off_contacts + b], fq.row1[ml.off_contacts + b], fq.blend);
-    }
-    if (b == 0) {
-        st3(root_pos + 3 * (size_t)q, query_root_pos(ml, fq, id));
-        st3(root_vel + 3 * (size_t)q, ld3(fq.row0 + ml.off_root_vel));
-        st3(root_ang_vel + 3 * (size_t)q, ld3(fq.row0 + ml.off_root_ang_vel));
-    }
-    for (int d = b; d < D; d += GRP) dof_vel[(size_t)q * D + d] = fq.row0[ml.off_dof_vel + d];
-}
-
-extern "C" int parc_calc_motion_frame(void *stream, parc_motion_lib_t mlib, int nq, const int64_t *ids, const float *times,
-                                      float *root_pos, float *root_rot, float *root_vel, float *root_ang_vel, float *joint_rot,
-                                      float *dof_vel, float *contacts) {
-    if (nq < 0 || mlib.num_bodies > PARC_MAX_BODIES || (mlib.row_stride & 3)) return PARC_EINVAL;
-    if (nq == 0) return PARC_OK;
-    int threads = 256, per = threads / GRP;
-    hipLaunchKernelGGL(motion_frame_kernel, dim3((nq + per - 1) / per), dim3(threads), 0, (hipStream_t)stream, mlib, nq, ids, times,
-                       root_pos, root_rot, root_vel, root_ang_vel, joint_rot, dof_vel, contacts);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-
-// =============================================================================================
-// Clip database build: MotionLib._load_motions  anim/motion_lib.py:264-290,405-423 and
-// KinCharModel.compute_frame_dof_vel  anim/kin_char_model.py:543-581, for ALL clips in one launch.
-// pass 1: pose rows (quaternions, root position, contacts); pass 2: finite-difference velocities.
-// =============================================================================================
-__global__ __launch_bounds__(256) void motion_rows_kernel(parc_char_model_t m, parc_motion_lib_t ml, int total_frames,
-                                                          const float *__restrict__ frames, const float *__restrict__ contacts,
-                                                          float *rows) {
-    int f = (blockIdx.x * blockDim.x + threadIdx.x) / GRP, b = threadIdx.x % GRP;
-    if (f >= total_frames || b >= m.num_bodies) return;
-    const float *fr = frames + (size_t)f * (6 + m.dof_size);
-    float *row = rows + (size_t)f * ml.row_stride;
-    q4 q;
-    if (b == 0) {
-        q = exp_map_to_quat_lib(mk3(fr[3], fr[4], fr[5]));        // motion_lib.py:418
-        st3(row + ml.off_pos, ld3(fr));
-    } else {
-        q = quat_pos(joint_dof_to_rot<true>(m, b, fr + 6, 1));     // motion_lib.py:420-421
-    }
-    st4(row + 4 * b, q);
-    row[ml.off_contacts + b] = contacts ? contacts[(size_t)f * m.num_bodies + b] : 0.f;
-}
-
-__global__ __launch_bounds__(256) void motion_vel_kernel(parc_char_model_t m, parc_motion_lib_t ml, int total_frames,
-                                                         const int32_t *__restrict__ frame_clip, const float *__restrict__ clip_fps,
-                                                         float *rows) {
-    int f = (blockIdx.x * blockDim.x + threadIdx.x) / GRP, b = threadIdx.x % GRP;
-    if (f >= total_frames || b >= m.num_bodies) return;
-    int c = frame_clip[f];
-    int nf = ml.num_frames[c], st = ml.start_idx[c];
-    float *row = rows + (size_t)f * ml.row_stride;
-    if (nf < 2) {
-        if (b == 0) {
-            st3(row + ml.off_root_vel, mk3(0.f, 0.f, 0.f));
-            st3(row + ml.off_root_ang_vel, mk3(0.f, 0.f, 0.f));
-        }
-        for (int d = b; d < m.dof_size; d += GRP) row[ml.off_dof_vel + d] = 0.f;
-        return;
-    }
-    int f0 = min(f - st, nf - 2) + st;  // the last frame repeats the previous difference (motion_lib.py:283,288)
-    const float *r0 = rows + (size_t)f0 * ml.row_stride, *r1 = r0 + ml.row_stride;
-    float fps = clip_fps[c];
-    float dt = 1.0f / fps;
-    if (b == 0) {
-        v3 p0 = ld3(r0 + ml.off_pos), p1 = ld3(r1 + ml.off_pos);
-        st3(row + ml.off_root_vel, fps * (p1 - p0));                                        // :281-283
-        v3 em = quat_to_exp_map(quat_mul(ld4(r1), quat_conj(ld4(r0))));                     // quat_diff :286-287
-        st3(row + ml.off_root_ang_vel, fps * em);
-    } else {
-        q4 dr = quat_unit(quat_pos(quat_mul(quat_conj(ld4(r0 + 4 * b)), ld4(r1 + 4 * b))));  // kin_char_model.py:558-559
-        int jt = m.joint_type[b];
-        if (jt == PARC_JOINT_HINGE) {
-            v3 e = quat_to_exp_map(dr);
-            row[ml.off_dof_vel + m.dof_idx[b]] = m.joint_axis[b][0] * (e.x / dt) + m.joint_axis[b][1] * (e.y / dt) + m.joint_axis[b][2] * (e.z / dt);
-        } else if (jt == PARC_JOINT_SPHERICAL) {
-            v3 e = quat_to_exp_map(dr);
-            float *o = row + ml.off_dof_vel + m.dof_idx[b];
-            o[0] = e.x / dt;
-            o[1] = e.y / dt;
-            o[2] = e.z / dt;
-        }
-    }
-}
-
-extern "C" int parc_motion_lib_build(void *stream, parc_char_model_t model, parc_motion_lib_t mlib, int total_frames,
-                                     const float *frames, const float *contacts, const int32_t *frame_clip, const float *clip_fps,
-                                     float *rows) {
-    if (!model_ok(model) || total_frames < 0 || mlib.num_bodies != model.num_bodies || (mlib.row_stride & 3)) return PARC_EINVAL;
-    if (total_frames == 0) return PARC_OK;
-    dim3 grid((total_frames + 15) / 16), block(256);
-    (void)hipMemsetAsync(rows, 0, sizeof(float) * (size_t)total_frames * mlib.row_stride, (hipStream_t)stream);
-    hipLaunchKernelGGL(motion_rows_kernel, grid, block, 0, (hipStream_t)stream, model, mlib, total_frames, frames, contacts, rows);
-    hipLaunchKernelGGL(motion_vel_kernel, grid, block, 0, (hipStream_t)stream, model, mlib, total_frames, frame_clip, clip_fps, rows);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-// =============================================================================================
-// K1 / K4 / K2 standalone (16 lanes per pose)
-// =============================================================================================
-__global__ __launch_bounds__(256) void dof_to_rot_kernel(parc_char_model_t m, int n, const float *__restrict__ dof, float *jrot) {
-    int i = (blockIdx.x * blockDim.x + threadIdx.x) / GRP, b = threadIdx.x % GRP;
-    if (i >= n || b == 0 || b >= m.num_bodies) return;
-    st4(jrot + ((size_t)i * (m.num_bodies - 1) + (b - 1)) * 4, joint_dof_to_rot(m, b, dof + (size_t)i * m.dof_size, 1));
-}
-
-__global__ __launch_bounds__(256) void rot_to_dof_kernel(parc_char_model_t m, int n, const float *__restrict__ jrot, float *dof) {
-    int i = (blockIdx.x * blockDim.x + threadIdx.x) / GRP, b = threadIdx.x % GRP;
-    if (i >= n || b == 0 || b >= m.num_bodies) return;
-    joint_rot_to_dof(m, b, ld4(jrot + ((size_t)i * (m.num_bodies - 1) + (b - 1)) * 4), dof + (size_t)i * m.dof_size);
-}
-
-__global__ __launch_bounds__(256) void fk_kernel(parc_char_model_t m, int n, const float *__restrict__ root_pos,
-                                                 const float *__restrict__ root_rot, const float *__restrict__ jrot,
-                                                 float *body_pos, float *body_rot) {
-    int i = (blockIdx.x * blockDim.x + threadIdx.x) / GRP, b = threadIdx.x % GRP;
-    bool live = i < n;
-    int ii = live ? i : 0;
-    q4 jq = mk4(0.f, 0.f, 0.f, 1.f);
-    if (b >= 1 && b < m.num_bodies) jq = ld4(jrot + ((size_t)ii * (m.num_bodies - 1) + (b - 1)) * 4);
-    v3 pos;
-    q4 rot;
-    group_fk(m, b, ld3(root_pos + 3 * (size_t)ii), ld4(root_rot + 4 * (size_t)ii), jq, pos, rot);
-    if (live && b < m.num_bodies) {
-        st3(body_pos + ((size_t)i * m.num_bodies + b) * 3, pos);
-        st4(body_rot + ((size_t)i * m.num_bodies + b) * 4, rot);
-    }
-}
-
-extern "C" int parc_dof_to_rot(void *stream, parc_char_model_t model, int n, const float *dof, float *joint_rot) {
-    if (n < 0 || !model_ok(model)) return PARC_EINVAL;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(dof_to_rot_kernel, dim3((n + 15) / 16), dim3(256), 0, (hipStream_t)stream, model, n, dof, joint_rot);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-extern "C" int parc_rot_to_dof(void *stream, parc_char_model_t model, int n, const float *joint_rot, float *dof) {
-    if (n < 0 || !model_ok(model)) return PARC_EINVAL;
-    if (n == 0) return PARC_OK;
-    (void)hipMemsetAsync(dof, 0, sizeof(float) * (size_t)n * model.dof_size, (hipStream_t)stream);
-    hipLaunchKernelGGL(rot_to_dof_kernel, dim3((n + 15) / 16), dim3(256), 0, (hipStream_t)stream, model, n, joint_rot, dof);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-extern "C" int parc_forward_kinematics(void *stream, parc_char_model_t model, int n, const float *root_pos, const float *root_rot,
-                                       const float *joint_rot, float *body_pos, float *body_rot) {
-    if (n < 0 || !model_ok(model)) return PARC_EINVAL;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(fk_kernel, dim3((n + 15) / 16), dim3(256), 0, (hipStream_t)stream, model, n, root_pos, root_rot, joint_rot,
-                       body_pos, body_rot);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-// =============================================================================================
-// Pose chain with its adjoint, one thread per frame: (root position, root exponential map, joint dofs) -> root quaternion, joint
-// rotations, body positions / rotations, and the vector-Jacobian product back.  This is what stage 2's motion optimiser
-// differentiates thousands of times per clip (tools/motion_opt/motion_optimization.py:203-213: exp_map_to_quat, KinCharModel.dof_to_rot,
-// forward_kinematics and their autograd); as torch ops it is ~190 autograd nodes per evaluation, here two launches.
-// Forward uses the library-precision maps (the values torch computes); the adjoint is exact for those formulas:
-//   q = a (x) b  bilinear          =>  g_a = g (x) conj(b),  g_b = conj(a) (x) g
-//   r = v + w t + u x t, t = 2 u x v  =>  g_w = g.t,  g_t = w g + g x u,  g_u = t x g + 2 v x g_t
-//   q = unit(n(axis) sin h, cos h), h = angle / 2   (torch_util.axis_angle_to_quat: both normalisations are projections at unit length)
-// =============================================================================================
-struct aa_grad { v3 g_axis; float g_angle; };
-
-PARC_DEV aa_grad axis_angle_to_quat_bwd(v3 axis, float angle, q4 q, q4 g) {
-    // through quat_unit: q = raw / |raw| with |raw| = 1 up to rounding -> g_raw = g - (g.q) q
-    const float gq = g.x * q.x + g.y * q.y + g.z * q.z + g.w * q.w;
-    const q4 gr = q4{g.x - gq * q.x, g.y - gq * q.y, g.z - gq * q.z, g.w - gq * q.w};
-    const float h = 0.5f * angle;
-    const float sh = sinf(h), ch = cosf(h);
-    const float na = fmaxf(sqrtf(dot3(axis, axis)), 1e-9f);
-    const v3 a = mk3(axis.x / na, axis.y / na, axis.z / na);
-    const v3 grv = mk3(gr.x, gr.y, gr.z);
-    aa_grad o;
-    o.g_angle = 0.5f * (ch * dot3(a, grv) - sh * gr.w);
-    // through normalize(axis): g_axis = (I - a a^T) (sin h g_v) / |axis|
-    const v3 ga = mk3(sh * grv.x, sh * grv.y, sh * grv.z);
-    const float gaa = dot3(ga, a);
-    o.g_axis = mk3((ga.x - gaa * a.x) / na, (ga.y - gaa * a.y) / na, (ga.z - gaa * a.z) / na);
-    return o;
-}
-
-// torch_util.exp_map_to_quat = axis_angle_to_quat(e / |e|, wrap(|e|)), z axis / angle 0 below 1e-5 (that branch is constant)
-PARC_DEV v3 exp_map_to_quat_bwd(v3 em, q4 q, q4 g) {
-    const float raw = sqrtf((em.x * em.x + em.y * em.y) + em.z * em.z);
-    const float ang = atan2f(sinf(raw), cosf(raw));
-    if (!(fabsf(ang) > 1e-5f)) return mk3(0.f, 0.f, 0.f);
-    const v3 a = mk3(em.x / raw, em.y / raw, em.z / raw);
-    const aa_grad ag = axis_angle_to_quat_bwd(a, ang, q, g);
-    // axis = e / raw: J^T g = (g - (g.a) a) / raw;  angle = wrap(raw): d/de = a
-    const float ga = dot3(ag.g_axis, a);
-    return mk3((ag.g_axis.x - ga * a.x) / raw + ag.g_angle * a.x, (ag.g_axis.y - ga * a.y) / raw + ag.g_angle * a.y,
-               (ag.g_axis.z - ga * a.z) / raw + ag.g_angle * a.z);
-}
-
-PARC_DEV q4 qadd(q4 a, q4 b) { return q4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
-
-// cotangent of q for r = quat_rotate(q, v) = v + w t + u x t, t = 2 u x v (u = q.xyz), given the cotangent g of r
-PARC_DEV q4 quat_rotate_bwd_q(q4 q, v3 v, v3 g) {
-    const v3 u = mk3(q.x, q.y, q.z);
-    const v3 t = 2.f * cross3(u, v);
-    const v3 gxu = cross3(g, u);
-    const v3 gt = mk3(q.w * g.x + gxu.x, q.w * g.y + gxu.y, q.w * g.z + gxu.z);
-    const v3 gu = cross3(t, g) + 2.f * cross3(v, gt);
-    return q4{gu.x, gu.y, gu.z, dot3(g, t)};
-}
-
-__global__ __launch_bounds__(64) void pose_chain_fwd_kernel(parc_char_model_t m, int n, const float *__restrict__ root_pos,
-                                                            const float *__restrict__ root_exp, const float *__restrict__ dof,
-                                                            float *root_quat, float *joint_rot, float *body_pos, float *body_rot) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int B = m.num_bodies;
-    q4 rot[PARC_MAX_BODIES];
-    v3 pos[PARC_MAX_BODIES];
-    rot[0] = exp_map_to_quat_lib(ld3(root_exp + 3 * (size_t)i));
-    pos[0] = ld3(root_pos + 3 * (size_t)i);
-    st4(root_quat + 4 * (size_t)i, rot[0]);
-    const float *d = dof + (size_t)i * m.dof_size;
-    for (int b = 1; b < B; ++b) {
-        const int p = m.parent[b];
-        const q4 jq = joint_dof_to_rot<true>(m, b, d, 1);
-        st4(joint_rot + ((size_t)i * (B - 1) + (b - 1)) * 4, jq);
-        const q4 loc = quat_mul(mk4(m.local_rotation[b][0], m.local_rotation[b][1], m.local_rotation[b][2], m.local_rotation[b][3]), jq);
-        rot[b] = quat_mul(rot[p], loc);
-        pos[b] = pos[p] + quat_rotate(rot[p], mk3(m.local_translation[b][0], m.local_translation[b][1], m.local_translation[b][2]));
-    }
-    for (int b = 0; b < B; ++b) {
-        st3(body_pos + ((size_t)i * B + b) * 3, pos[b]);
-        st4(body_rot + ((size_t)i * B + b) * 4, rot[b]);
-    }
-}
-
-__global__ __launch_bounds__(64) void pose_chain_bwd_kernel(parc_char_model_t m, int n, const float *__restrict__ root_exp,
-                                                            const float *__restrict__ dof, const float *__restrict__ g_root_quat,
-                                                            const float *__restrict__ g_joint_rot, const float *__restrict__ g_body_pos,
-                                                            const float *__restrict__ g_body_rot, float *g_root_pos, float *g_root_exp,
-                                                            float *g_dof) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int B = m.num_bodies;
-    q4 rot[PARC_MAX_BODIES], jq[PARC_MAX_BODIES], loc[PARC_MAX_BODIES], grot[PARC_MAX_BODIES];
-    v3 gpos[PARC_MAX_BODIES];
-    const v3 em = ld3(root_exp + 3 * (size_t)i);
-    const float *d = dof + (size_t)i * m.dof_size;
-    float *gd = g_dof + (size_t)i * m.dof_size;
-    for (int k = 0; k < m.dof_size; ++k) gd[k] = 0.f;
-    rot[0] = exp_map_to_quat_lib(em);
-    for (int b = 1; b < B; ++b) {
-        jq[b] = joint_dof_to_rot<true>(m, b, d, 1);
-        loc[b] = quat_mul(mk4(m.local_rotation[b][0], m.local_rotation[b][1], m.local_rotation[b][2], m.local_rotation[b][3]), jq[b]);
-        rot[b] = quat_mul(rot[m.parent[b]], loc[b]);
-    }
-    for (int b = 0; b < B; ++b) {
-        gpos[b] = ld3(g_body_pos + ((size_t)i * B + b) * 3);
-        grot[b] = ld4(g_body_rot + ((size_t)i * B + b) * 4);
-    }
-    for (int b = B - 1; b >= 1; --b) {          // children before parents: a body's index exceeds its parent's
-        const int p = m.parent[b];
-        // pos[b] = pos[p] + rotate(rot[p], t_b)
-        gpos[p] = gpos[p] + gpos[b];
-        grot[p] = qadd(grot[p], quat_rotate_bwd_q(rot[p], mk3(m.local_translation[b][0], m.local_translation[b][1], m.local_translation[b][2]), gpos[b]));
-        // rot[b] = rot[p] (x) loc[b]
-        grot[p] = qadd(grot[p], quat_mul(grot[b], quat_conj(loc[b])));
-        const q4 gloc = quat_mul(quat_conj(rot[p]), grot[b]);
-        // loc[b] = lrot (x) jq[b], + the cotangent handed in for the joint rotation itself
-        const q4 lr = mk4(m.local_rotation[b][0], m.local_rotation[b][1], m.local_rotation[b][2], m.local_rotation[b][3]);
-        const q4 gj = qadd(quat_mul(quat_conj(lr), gloc), ld4(g_joint_rot + ((size_t)i * (B - 1) + (b - 1)) * 4));
-        const int jt = m.joint_type[b], d0 = m.dof_idx[b];
-        if (jt == PARC_JOINT_HINGE) {
-            const v3 ax = mk3(m.joint_axis[b][0], m.joint_axis[b][1], m.joint_axis[b][2]);
-            gd[d0] = axis_angle_to_quat_bwd(ax, d[d0], jq[b], gj).g_angle;
-        } else if (jt == PARC_JOINT_SPHERICAL) {
-            const v3 ge = exp_map_to_quat_bwd(mk3(d[d0], d[d0 + 1], d[d0 + 2]), jq[b], gj);
-            gd[d0] = ge.x;
-            gd[d0 + 1] = ge.y;
-            gd[d0 + 2] = ge.z;
-        }
-    }
-    st3(g_root_pos + 3 * (size_t)i, gpos[0]);
-    st3(g_root_exp + 3 * (size_t)i, exp_map_to_quat_bwd(em, rot[0], qadd(grot[0], ld4(g_root_quat + 4 * (size_t)i))));
-}
-
-// Angle between two rotations, torch_util.quat_diff_angle(q0, q1) = angle of q1 (x) conj(q0) (util/torch_util.py:421-431,68-88: the
-// w >= 0 representative, 2 atan2(|v|, w), 0 below |v| = 1e-5), and its adjoint; one thread per pair.  The optimiser evaluates it for
-// the root, every joint and every body-to-next-frame pair of every frame.
-__global__ __launch_bounds__(256) void quat_diff_angle_kernel(size_t n, const float *__restrict__ q0, const float *__restrict__ q1, float *angle) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const q4 d = quat_mul(ld4(q1 + 4 * i), quat_conj(ld4(q0 + 4 * i)));
-    const float s = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
-    angle[i] = s > 1e-5f ? 2.0f * atan2f(s, fabsf(d.w)) : 0.f;
-}
-
-__global__ __launch_bounds__(256) void quat_diff_angle_grad_kernel(size_t n, const float *__restrict__ q0, const float *__restrict__ q1,
-                                                                   const float *__restrict__ g_angle, float *g_q0, float *g_q1) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const q4 a = ld4(q0 + 4 * i), b = ld4(q1 + 4 * i);
-    const q4 d = quat_mul(b, quat_conj(a));
-    const float s = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
-    q4 ga = mk4(0.f, 0.f, 0.f, 0.f), gb = ga;
-    if (s > 1e-5f) {
-        const float sg = d.w < 0.f ? -1.0f : 1.0f;           // quat_pos: the representative with w >= 0
-        const float w = sg * d.w, den = s * s + w * w, g = g_angle[i];
-        const float gs = 2.0f * w / den * g / s;               // d angle / d|v| * (v / |v|), on the flipped vector part ...
-        const q4 gd = q4{sg * gs * (sg * d.x), sg * gs * (sg * d.y), sg * gs * (sg * d.z), sg * (-2.0f * s / den * g)};     // ... and flipped back
-        gb = quat_mul(gd, a);                                   // d = b (x) conj(a):  g_b = g_d (x) a
-        const q4 gc = quat_mul(quat_conj(b), gd);               //                     g_conj(a) = conj(b) (x) g_d
-        ga = q4{-gc.x, -gc.y, -gc.z, gc.w};
-    }
-    st4(g_q0 + 4 * i, ga);
-    st4(g_q1 + 4 * i, gb);
-}
-
-extern "C" int parc_quat_diff_angle(void *stream, int64_t n, const float *q0, const float *q1, float *angle) {
-    if (n < 0) return PARC_EINVAL;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(quat_diff_angle_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (size_t)n, q0, q1, angle);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-extern "C" int parc_quat_diff_angle_grad(void *stream, int64_t n, const float *q0, const float *q1, const float *g_angle, float *g_q0, float *g_q1) {
-    if (n < 0) return PARC_EINVAL;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(quat_diff_angle_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (size_t)n, q0, q1, g_angle,
-                       g_q0, g_q1);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-// The frame-to-frame terms of stage 2's motion loss and their adjoint: the bodies live in parc_moopt_core.h (tt_forward_body /
-// tt_backward_body), shared with the packed-motions pair of parc_moopt.hip.  One thread per (frame, body).
-__global__ __launch_bounds__(256) void temporal_terms_kernel(int T, int B, const float *__restrict__ pos, const float *__restrict__ rot_err_sq,
-                                                             const float *__restrict__ src_vel, const float *__restrict__ keep,
-                                                             const float *__restrict__ pair_contact, tt_args a, float *partial) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= T * B) return;
-    const int t = i / B, b = i - t * B;
-    float sm, sl, jl;
-    tt_forward_body(T, B, t, b, i, pos, rot_err_sq, src_vel, keep, pair_contact, a, sm, sl, jl);
-    const size_t n = (size_t)T * B;
-    partial[i] = sm;
-    partial[n + i] = sl;
-    partial[2 * n + i] = jl;
-}
-
-__global__ __launch_bounds__(256) void temporal_terms_grad_kernel(int T, int B, const float *__restrict__ pos, const float *__restrict__ rot_err_sq,
-                                                                  const float *__restrict__ src_vel, const float *__restrict__ keep,
-                                                                  const float *__restrict__ pair_contact, tt_args a,
-                                                                  const float *__restrict__ w /* cotangents of the 3 sums */, float *g_pos,
-                                                                  float *g_rot_err_sq) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= T * B) return;
-    const int t = i / B, b = i - t * B;
-    const float w0 = w[0], w1 = w[1], w2 = w[2];
-    float g_r;
-    bool has_r;
-    const v3 g = tt_backward_body(T, B, t, b, i, pos, rot_err_sq, src_vel, keep, pair_contact, a, w0, w1, w2, g_r, has_r);
-    st3(g_pos + (size_t)i * 3, g);
-    if (has_r) g_rot_err_sq[i] = g_r;
-}
-
-extern "C" int parc_temporal_terms(void *stream, int n_frames, int num_bodies, const float *body_pos, const float *rot_err_sq, const float *src_vel,
-                                   const float *keep, const float *pair_contact, float c, float c2, float jerk_limit, float *partial) {
-    if (n_frames < 0 || num_bodies <= 0) return PARC_EINVAL;
-    const int n = n_frames * num_bodies;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(temporal_terms_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_frames, num_bodies, body_pos, rot_err_sq,
-                       src_vel, keep, pair_contact, tt_args{c, c2, jerk_limit}, partial);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-extern "C" int parc_temporal_terms_grad(void *stream, int n_frames, int num_bodies, const float *body_pos, const float *rot_err_sq,
-                                        const float *src_vel, const float *keep, const float *pair_contact, float c, float c2, float jerk_limit,
-                                        const float *cotangents, float *g_body_pos, float *g_rot_err_sq) {
-    if (n_frames < 0 || num_bodies <= 0) return PARC_EINVAL;
-    const int n = n_frames * num_bodies;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(temporal_terms_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_frames, num_bodies, body_pos,
-                       rot_err_sq, src_vel, keep, pair_contact, tt_args{c, c2, jerk_limit}, cotangents, g_body_pos, g_rot_err_sq);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-// Sample points of the bodies in the world frame, x[t, p] = pos[t, owner(p)] + rotate(rot[t, owner(p)], local[p]), and the adjoint
-// (the points of a body are contiguous: body b owns [start[b], start[b + 1])), one thread per point / per (frame, body).
-__global__ __launch_bounds__(256) void body_points_world_kernel(int n_frames, int B, int P, const float *__restrict__ body_pos,
-                                                                const float *__restrict__ body_rot, const float *__restrict__ local,
-                                                                const int32_t *__restrict__ owner, float *world) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)n_frames * P) return;
-    const int t = (int)(i / P), p = (int)(i - (size_t)t * P), b = owner[p];
-    const v3 x = ld3(body_pos + ((size_t)t * B + b) * 3) + quat_rotate(ld4(body_rot + ((size_t)t * B + b) * 4), ld3(local + 3 * (size_t)p));
-    st3(world + i * 3, x);
-}
-
-__global__ __launch_bounds__(256) void body_points_world_grad_kernel(int n_frames, int B, int P, const float *__restrict__ body_rot,
-                                                                     const float *__restrict__ local, const int32_t *__restrict__ start,
-                                                                     const float *__restrict__ g_world, float *g_body_pos, float *g_body_rot) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)n_frames * B) return;
-    const int t = (int)(i / B), b = (int)(i - (size_t)t * B);
-    const q4 q = ld4(body_rot + i * 4);
-    v3 gp = mk3(0.f, 0.f, 0.f);
-    q4 gq = mk4(0.f, 0.f, 0.f, 0.f);
-    for (int p = start[b]; p < start[b + 1]; ++p) {
-        const v3 g = ld3(g_world + ((size_t)t * P + p) * 3);
-        gp = gp + g;
-        gq = qadd(gq, quat_rotate_bwd_q(q, ld3(local + 3 * (size_t)p), g));
-    }
-    st3(g_body_pos + i * 3, gp);
-    st4(g_body_rot + i * 4, gq);
-}
-
-extern "C" int parc_body_points_world(void *stream, int n_frames, int num_bodies, int num_points, const float *body_pos, const float *body_rot,
-                                      const float *local, const int32_t *owner, float *world) {
-    if (n_frames < 0 || num_bodies <= 0 || num_points < 0) return PARC_EINVAL;
-    const size_t n = (size_t)n_frames * num_points;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(body_points_world_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_frames, num_bodies, num_points,
-                       body_pos, body_rot, local, owner, world);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-extern "C" int parc_body_points_world_grad(void *stream, int n_frames, int num_bodies, int num_points, const float *body_rot, const float *local,
-                                           const int32_t *start, const float *g_world, float *g_body_pos, float *g_body_rot) {
-    if (n_frames < 0 || num_bodies <= 0 || num_points < 0) return PARC_EINVAL;
-    const size_t n = (size_t)n_frames * num_bodies;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(body_points_world_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n_frames, num_bodies,
-                       num_points, body_rot, local, start, g_world, g_body_pos, g_body_rot);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-extern "C" int parc_pose_chain_forward(void *stream, parc_char_model_t model, int n, const float *root_pos, const float *root_exp,
-                                       const float *dof, float *root_quat, float *joint_rot, float *body_pos, float *body_rot) {
-    if (n < 0 || !model_ok(model)) return PARC_EINVAL;
-    for (int b = 1; b < model.num_bodies; ++b)
-        if (model.parent[b] < 0 || model.parent[b] >= b) return PARC_EUNSUPPORTED;      // the sweeps rely on parents-first order
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(pose_chain_fwd_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, model, n, root_pos, root_exp, dof, root_quat,
-                       joint_rot, body_pos, body_rot);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-extern "C" int parc_pose_chain_backward(void *stream, parc_char_model_t model, int n, const float *root_exp, const float *dof,
-                                        const float *g_root_quat, const float *g_joint_rot, const float *g_body_pos, const float *g_body_rot,
-                                        float *g_root_pos, float *g_root_exp, float *g_dof) {
-    if (n < 0 || !model_ok(model)) return PARC_EINVAL;
-    for (int b = 1; b < model.num_bodies; ++b)
-        if (model.parent[b] < 0 || model.parent[b] >= b) return PARC_EUNSUPPORTED;
-    if (n == 0) return PARC_OK;
-    hipLaunchKernelGGL(pose_chain_bwd_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, model, n, root_exp, dof, g_root_quat,
-                       g_joint_rot, g_body_pos, g_body_rot, g_root_pos, g_root_exp, g_dof);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
 }
 
 // =============================================================================================
@@ -1975,123 +1119,6 @@ extern "C" int parc_update_fail_rates(void *stream, int n_envs, int n_motions, c
     if (n_envs < 0 || n_motions <= 0) return PARC_EINVAL;
     hipLaunchKernelGGL(fail_rate_kernel, dim3(n_motions), dim3(FR_THREADS), 0, (hipStream_t)stream, n_envs, n_motions, motion_ids, done_kind,
                        ema_w, fail_rates);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-// =============================================================================================
-// K16 TD(lambda): one env per lane, backward recurrence in a register; [T,N] loads coalesce over envs
-// =============================================================================================
-__global__ __launch_bounds__(256) void td_lambda_kernel(int T, int N, const float *__restrict__ r, const float *__restrict__ nv,
-                                                        const int32_t *__restrict__ done, float discount, float lam, float *ret) {
-    int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= N) return;
-    size_t i = (size_t)(T - 1) * N + e;
-    float next_ret = r[i] + discount * nv[i];
-    ret[i] = next_ret;
-    for (int t = T - 2; t >= 0; --t) {
-        i = (size_t)t * N + e;
-        float reset = done[i] != PARC_DONE_NULL ? 1.f : 0.f;
-        float cl = lam * (1.0f - reset);
-        float cur = r[i] + discount * ((1.0f - cl) * nv[i] + cl * next_ret);
-        ret[i] = cur;
-        next_ret = cur;
-    }
-}
-
-extern "C" int parc_td_lambda_return(void *stream, int T, int N, const float *reward, const float *next_vals, const int32_t *done,
-                                     float discount, float td_lambda, float *ret) {
-    if (T <= 0 || N < 0) return PARC_EINVAL;
-    if (N == 0) return PARC_OK;
-    hipLaunchKernelGGL(td_lambda_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, N, reward, next_vals, done,
-                       discount, td_lambda, ret);
-    PARC_CHECK_LAUNCH();
-    return PARC_OK;
-}
-
-// =============================================================================================
-// K17 advantage normalisation: deterministic two-stage (sum, sumsq, count) in fp64, then normalise.
-// Non-finite input as torch.std_mean / clamp_min / clamp (dm_ppo_agent.py:393-400): no selected sample -> mean and std NaN, one -> std
-// NaN, a NaN or Inf among the selected advantages -> both NaN (torch's running mean meets inf - inf); a NaN std makes every advantage
-// NaN; a NaN return or value of an unselected sample stays in its element.
-// =============================================================================================
-#define ADV_BLOCKS 1024
-__global__ __launch_bounds__(256) void adv_partial_kernel(int n, const float *__restrict__ ret, const float *__restrict__ vals,
-                                                          const float *__restrict__ mask, double *ws) {
-    __shared__ double sh[3][256];
-    double s = 0.0, ss = 0.0, c = 0.0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        if (mask[i] == 1.0f) {
-            double a = (double)(ret[i] - vals[i]);
-            s += a;
-            ss += a * a;
-            c += 1.0;
-        }
-    }
-    sh[0][threadIdx.x] = s;
-    sh[1][threadIdx.x] = ss;
-    sh[2][threadIdx.x] = c;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + st];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + st];
-            sh[2][threadIdx.x] += sh[2][threadIdx.x + st];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        ws[blockIdx.x] = sh[0][0];
-        ws[ADV_BLOCKS + blockIdx.x] = sh[1][0];
-        ws[2 * ADV_BLOCKS + blockIdx.x] = sh[2][0];
-    }
-}
-
-__global__ __launch_bounds__(256) void adv_apply_kernel(int n, int nblocks, const float *__restrict__ ret, const float *__restrict__ vals,
-                                                        float clip, const double *__restrict__ ws, float *out, float *mean_std) {
-    __shared__ double sh[3][256];
-    double s = 0.0, ss = 0.0, c = 0.0;
-    for (int i = threadIdx.x; i < nblocks; i += 256) {
-        s += ws[i];
-        ss += ws[ADV_BLOCKS + i];
-        c += ws[2 * ADV_BLOCKS + i];
-    }
-    sh[0][threadIdx.x] = s;
-    sh[1][threadIdx.x] = ss;
-    sh[2][threadIdx.x] = c;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if ((int)threadIdx.x < st) {
-            sh[0][threadIdx.x] += sh[0][threadIdx.x + st];
-            sh[1][threadIdx.x] += sh[1][threadIdx.x + st];
-            sh[2][threadIdx.x] += sh[2][threadIdx.x + st];
-        }
-        __syncthreads();
-    }
-    double cnt = sh[2][0];
-    double mean = sh[0][0] / cnt;                                          // (cnt 0: 0 / 0)
-    double var = (sh[1][0] - cnt * mean * mean) / (cnt - 1.0);             // torch.std_mean: unbiased  (cnt 1: 0 / 0)
-    var = var < 0.0 ? 0.0 : var;                                           // (a NaN passes)
-    if (!(sh[1][0] < (double)INFINITY)) mean = (double)NAN;                // (fp32 squares cannot overflow a double: a non-finite sample)
-    float meanf = (float)mean, stdf = (float)sqrt(var);
-    float den = stdf < 1e-5f ? 1e-5f : stdf;                               // torch.clamp_min: NaN stays NaN
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        mean_std[0] = meanf;
-        mean_std[1] = stdf;
-    }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        float a = ((ret[i] - vals[i]) - meanf) / den;
-        out[i] = a < -clip ? -clip : (a > clip ? clip : a);              // torch.clamp: NaN stays NaN
-    }
-}
-
-extern "C" int parc_adv_normalize(void *stream, int n, const float *ret, const float *vals, const float *rand_action_mask, float clip,
-                                  float *norm_adv, float *mean_std_out, double *workspace) {
-    if (n <= 0 || !workspace) return PARC_EINVAL;
-    int nb = (n + 255) / 256;
-    if (nb > ADV_BLOCKS) nb = ADV_BLOCKS;
-    hipLaunchKernelGGL(adv_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, n, ret, vals, rand_action_mask, workspace);
-    hipLaunchKernelGGL(adv_apply_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, n, nb, ret, vals, clip, workspace, norm_adv, mean_std_out);
     PARC_CHECK_LAUNCH();
     return PARC_OK;
 }

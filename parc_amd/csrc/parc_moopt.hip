@@ -1,17 +1,12 @@
 // Kernels of the batched motion optimiser (include/parc_moopt.h): M motions packed along the frame axis descend together, so the
 // terrain query takes a terrain per row, the frame-to-frame terms are cut at motion seams and per-frame partials are folded per motion.
-// The bodies are in parc_moopt_core.h (shared with parc_kin.hip and with the host build of the CPU tests); here are the thread maps.
+// The bodies are in parc_moopt_core.h (shared with parc_pose_opt.hip and with the host build of the CPU tests); here are the thread maps.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/parc_moopt.h"
+#include "parc_launch.h"
 #include "parc_moopt_core.h"
-
-#define MOOPT_CHECK_LAUNCH()                        \
-    do {                                            \
-        hipError_t _e = hipGetLastError();          \
-        if (_e != hipSuccess) return (int)_e;       \
-    } while (0)
 
 #define RAGGED_THREADS 64       // as points_hf_sdf_kernel: the window scan diverges per point, a workgroup of one wave retires early
 
@@ -92,7 +87,7 @@ extern "C" int parc_points_hf_sdf_ragged(void *stream, int64_t n_rows, int point
     if (!ragged_grid(n_rows, points_per_row, n_total, blocks)) return PARC_EUNSUPPORTED;
     hipLaunchKernelGGL(points_hf_sdf_ragged_kernel, dim3(blocks), dim3(RAGGED_THREADS), 0, (hipStream_t)stream, n_total, points_per_row, points,
                        row_terrain, n_terrains, table, pool, inverted, radius, out, out_cell);
-    MOOPT_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 
@@ -107,7 +102,7 @@ extern "C" int parc_points_hf_sdf_ragged_grad(void *stream, int64_t n_rows, int 
     if (!ragged_grid(n_rows, points_per_row, n_total, blocks)) return PARC_EUNSUPPORTED;
     hipLaunchKernelGGL(points_hf_sdf_ragged_grad_kernel, dim3(blocks), dim3(RAGGED_THREADS), 0, (hipStream_t)stream, n_total, points_per_row, points,
                        row_terrain, n_terrains, table, pool, inverted, cell, g_out, g_points);
-    MOOPT_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 
@@ -119,7 +114,7 @@ extern "C" int parc_temporal_terms_seg(void *stream, int n_frames, int num_bodie
     const int n = n_frames * num_bodies;
     hipLaunchKernelGGL(temporal_terms_seg_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_frames, num_bodies, n_motions, seg_start,
                        seg_of_frame, body_pos, rot_err_sq, src_vel, keep, pair_contact, tt_args{c, c2, jerk_limit}, partial);
-    MOOPT_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 
@@ -135,7 +130,7 @@ extern "C" int parc_temporal_terms_seg_grad(void *stream, int n_frames, int num_
     hipLaunchKernelGGL(temporal_terms_seg_grad_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_frames, num_bodies, n_motions,
                        seg_start, seg_of_frame, body_pos, rot_err_sq, src_vel, keep, pair_contact, tt_args{c, c2, jerk_limit}, cotangents, g_body_pos,
                        g_rot_err_sq);
-    MOOPT_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 
@@ -145,7 +140,7 @@ extern "C" int parc_segment_sums(void *stream, int n_planes, int n_rows, int wid
     if (rc != PARC_OK) return rc == PARC_MOOPT_NOTHING ? PARC_OK : rc;
     hipLaunchKernelGGL(segment_sums_kernel, dim3(n_motions, n_planes), dim3(PARC_MOOPT_SUM_LANES), 0, (hipStream_t)stream, n_rows, width, n_motions,
                        seg_start, values, out);
-    MOOPT_CHECK_LAUNCH();
+    PARC_CHECK_LAUNCH();
     return PARC_OK;
 }
 

@@ -1,4 +1,4 @@
-// Bodies of the motion optimiser's kernels, shared by the device (hipcc: parc_kin.hip, parc_moopt.hip) and the host (g++: the CPU
+// Bodies of the motion optimiser's kernels, shared by the device (hipcc: parc_pose_opt.hip, parc_moopt.hip) and the host (g++: the CPU
 // tests, tests/tools/moopt_host.cpp):
 //   * the frame-to-frame terms of stage 2's motion loss and their adjoint (tt_*), for one motion (parc_temporal_terms) and for motions
 //     packed along the frame axis (parc_temporal_terms_seg);

@@ -12,6 +12,7 @@
 // netstats_abs_colsum_kernel and netstats_dormant_kernel run once per rollout / per report.
 #include <hip/hip_runtime.h>
 
+#include "parc_launch.h"
 #include "parc_netstats_core.h"
 
 using namespace parc_ns;
@@ -134,19 +135,18 @@ extern "C" int parc_netstats_update(void *stream, int64_t rows, parc_netstats_ta
     hipLaunchKernelGGL(netstats_partial_kernel, dim3((max_dim + PARC_NETSTATS_COLS - 1) / PARC_NETSTATS_COLS, chunks, table.num_layers + 1),
                        dim3(NS_THREADS), 0, (hipStream_t)stream, (int)rows, table, chunks, rows * A, mean, mean_net_acts, eta, gain,
                        (float4 *)workspace);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    PARC_CHECK_LAUNCH();
     hipLaunchKernelGGL(netstats_finalize_kernel, dim3((max_dim + NS_THREADS - 1) / NS_THREADS, table.num_layers), dim3(NS_THREADS), 0,
                        (hipStream_t)stream, (int)rows, table, chunks, eta, gain, workspace);
-    e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_netstats_abs_colsum(void *stream, int rows, int dim, const float *w, float *out) {
     if (rows < 1 || dim < 1 || !w || !out) return PARC_EINVAL;
     hipLaunchKernelGGL(netstats_abs_colsum_kernel, dim3((dim + NS_THREADS - 1) / NS_THREADS), dim3(NS_THREADS), 0, (hipStream_t)stream, rows, dim, w, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_netstats_dormant_count(void *stream, parc_netstats_table_t table, int64_t n_mean, const float *mean_net_acts, float threshold,
@@ -154,8 +154,8 @@ extern "C" int parc_netstats_dormant_count(void *stream, parc_netstats_table_t t
     if (check_table(table) != PARC_OK || !counts || n_mean < 0 || n_mean > 2147483647LL || (n_mean > 0 && !mean_net_acts)) return PARC_EINVAL;
     hipLaunchKernelGGL(netstats_dormant_kernel, dim3(table.num_layers + 1), dim3(NS_THREADS), 0, (hipStream_t)stream, table, n_mean, mean_net_acts,
                        threshold, counts);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_netstats_abi(void) { return 1; }

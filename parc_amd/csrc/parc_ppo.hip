@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "../../include/parc_hip.h"
+#include "parc_launch.h"
 
 #define PPO_THREADS 256
 #define PPO_MAX_A 64
@@ -294,8 +295,8 @@ static int ppo_loss_impl(void *stream, int B, int A, const float *mean, const fl
     hipLaunchKernelGGL(ppo_reduce_kernel, dim3(1), dim3(PPO_RED_THREADS), 0, st, B, A, nblk, logstd, cfg, workspace, g_logstd, out);
     const int n = B * A;
     hipLaunchKernelGGL(ppo_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, B, out, g_mean, g_pred);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_ppo_workspace_floats(int B) { return ((B + PPO32_SPB - 1) / PPO32_SPB) * PPO_W; }      // (the finer of the two block sizes)
@@ -352,8 +353,8 @@ extern "C" int parc_record_step(void *stream, int n_envs, const int64_t *head, i
     unsigned gx = (unsigned)((units + 255) / 256);
     if (gx > 2048u) gx = 2048u;                                          // grid-stride beyond that
     hipLaunchKernelGGL(record_step_kernel, dim3(gx, (unsigned)n_fields), dim3(256), 0, (hipStream_t)stream, n_envs, head, args);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -427,8 +428,8 @@ extern "C" int parc_rng_step(void *stream, uint64_t seed, uint64_t *state, float
     if (quads == 0 && !tick_cell) return PARC_OK;
     hipLaunchKernelGGL(rng_step_kernel, dim3((unsigned)((quads + 255) / 256 > 0 ? (quads + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, seed,
                        state, uniform_out, n_uniform, normal_out, n_normal, tick_cell, tick_mod);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -525,8 +526,8 @@ extern "C" int parc_return_tracker_update(void *stream, int n_envs, int K, const
     hipLaunchKernelGGL(return_tracker_kernel, dim3(groups), dim3(TRK_THREADS), 0, (hipStream_t)stream, n_envs, K, rewards, reward_stride, done,
                        return_buf, ep_len, eps_per_env, workspace);
     hipLaunchKernelGGL(return_tracker_fold_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, groups, K, workspace, mean_return, mean_ep_len, episodes);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -545,8 +546,8 @@ extern "C" int parc_scale_by_clipped_norm(void *stream, int64_t n, float *x, con
     size_t blocks = ((size_t)n + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(scale_by_clipped_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (size_t)n, x, norm, max_norm);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -620,8 +621,8 @@ extern "C" int parc_sgd_momentum_step(void *stream, int64_t n, float *params, co
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(sgd_momentum_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (size_t)n, params, grad, momentum_buf, workspace, max_norm,
                        lr, momentum, weight_decay, norm_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -727,8 +728,8 @@ extern "C" int parc_adamw_step(void *stream, int64_t n, float *params, const flo
     if (blocks > ADAMW_MAX_BLOCKS) blocks = ADAMW_MAX_BLOCKS;
     hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (size_t)n, n4, params, grad, exp_avg, exp_avg_sq, workspace, max_norm,
                        c, norm_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -759,8 +760,8 @@ extern "C" int parc_normalize_clamp(void *stream, int64_t rows, int dim, const f
     if (blocks > 8192) blocks = 8192;
     hipLaunchKernelGGL(normalize_clamp_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n4, dim / 4, (const float4 *)x,
                        (const float4 *)mean, (const float4 *)stdv, clip, (float4 *)out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -877,8 +878,8 @@ extern "C" int parc_obs_ingest(void *stream, int64_t rows, int dim, const float 
     if (acc)
         hipLaunchKernelGGL(moments_final_kernel, dim3((2 * dim4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, chunks, dim4,
                            (const float4 *)workspace, (float4 *)acc);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_moments_accumulate(void *stream, int64_t rows, int dim, const float *x, float *acc, float *workspace) {
@@ -890,8 +891,8 @@ extern "C" int parc_moments_accumulate(void *stream, int64_t rows, int dim, cons
                        (float4 *)workspace);
     hipLaunchKernelGGL(moments_final_kernel, dim3((2 * dim4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, chunks, dim4,
                        (const float4 *)workspace, (float4 *)acc);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -975,8 +976,8 @@ extern "C" int parc_weighted_colsum(void *stream, int64_t rows, int dim, const f
         hipLaunchKernelGGL(weighted_colsum_partial_kernel, dim3((dim4 + 63) / 64, chunks), dim3(256), 0, (hipStream_t)stream, (int)rows, dim4,
                            (const float4 *)x, w, (float4 *)workspace);
     hipLaunchKernelGGL(colsum_final_kernel, dim3((dim + 255) / 256), dim3(256), 0, (hipStream_t)stream, chunks, dim, workspace, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int64_t parc_relu_bwd_workspace_floats(int64_t rows, int dim) {
@@ -993,8 +994,8 @@ extern "C" int parc_relu_bwd_bias_grad(void *stream, int64_t rows, int dim, floa
         hipLaunchKernelGGL(relu_bwd_bias_partial_kernel, dim3((dim4 + 63) / 64, chunks), dim3(256), 0, (hipStream_t)stream, (int)rows, dim4,
                            (float4 *)gy, (const float4 *)y, (float4 *)workspace);
     hipLaunchKernelGGL(colsum_final_kernel, dim3((dim + 255) / 256), dim3(256), 0, (hipStream_t)stream, chunks, dim, workspace, db);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // =============================================================================================
@@ -1081,13 +1082,13 @@ extern "C" int parc_action_head(void *stream, int n, int A, const float *mean, c
         action_record_t none = {};
         hipLaunchKernelGGL(action_head32_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, A, mean, logstd, noise,
                            explore, a_mean, a_std, action, logp, none);
-        hipError_t e32 = hipGetLastError();
-        return e32 == hipSuccess ? PARC_OK : (int)e32;
+        PARC_CHECK_LAUNCH();
+        return PARC_OK;
     }
     hipLaunchKernelGGL(action_head_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, A, mean, logstd, noise, explore, a_mean,
                        a_std, action, logp);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_action_head_record(void *stream, int n, int A, const float *mean, const float *logstd, const float *noise, const float *explore,
@@ -1099,6 +1100,6 @@ extern "C" int parc_action_head_record(void *stream, int n, int A, const float *
     const long long threads = (long long)n * 32;
     hipLaunchKernelGGL(action_head32_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, A, mean, logstd, noise, explore,
                        a_mean, a_std, action, logp, rec);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }

@@ -4,6 +4,7 @@
 // per character.  All ray arithmetic is parc_render_core.h, shared with the host build of the tests.
 #include <hip/hip_runtime.h>
 
+#include "parc_launch.h"
 #include "parc_render_core.h"
 
 using namespace parc_rc;
@@ -51,8 +52,8 @@ extern "C" int parc_render(void *stream, parc_terrain_t terrain, const parc_rend
     const dim3 grid((width + RENDER_TILE - 1) / RENDER_TILE, (height + RENDER_TILE - 1) / RENDER_TILE, n_views);
     hipLaunchKernelGGL(render_kernel, grid, dim3(RENDER_TILE, RENDER_TILE), 0, (hipStream_t)stream, terrain, *scene, views, width, height,
                        root_state, rigid_body_state, ref_body_pos, ref_body_rot, contact_forces, env_offsets, n_envs, rgba, depth, ids);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_render_abi(void) { return 1; }

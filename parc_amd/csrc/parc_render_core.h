@@ -6,7 +6,7 @@
 // Conventions
 //   * rays: origin o, unit direction d, hits at o + t d with t > 0.  Only ENTRIES count: a ray that starts inside a solid does not
 //     see that solid's surface from within.
-//   * terrain: the column field of hf_lookup (parc_kin.hip).  Cell (i, j) is centred at min + (i, j) * dx, owns rint((p - min) / dx),
+//   * terrain: the column field of hf_lookup (parc_hf_lookup.h).  Cell (i, j) is centred at min + (i, j) * dx, owns rint((p - min) / dx),
 //     i.e. the square [i - 1/2, i + 1/2) x [j - 1/2, j + 1/2) in grid units, has its top at hf[i, j] and reaches down without end, so
 //     neighbours of different height are joined by vertical walls.  Traversal: a 2-D DDA over the cells from where the ray enters the
 //     grid's bounding box; outside the grid there is nothing.  In grid units u = (x - min_x) / dx + 1/2 cell i is floor(u).

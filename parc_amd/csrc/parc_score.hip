@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "parc_fk_group.h"
+#include "parc_launch.h"
 #include "parc_score_core.h"
 
 using namespace parc_sc;
@@ -91,12 +92,11 @@ extern "C" int parc_motion_score(void *stream, parc_char_model_t model, int B, i
     hipLaunchKernelGGL(motion_score_frames_kernel, dim3((F + PARC_SCORE_TILE - 1) / PARC_SCORE_TILE, B), dim3(SCORE_THREADS), 0, (hipStream_t)stream,
                        model, F, num_frames, root_pos, root_rot, joint_rot, contacts, n_points, local, start, terrain, base_z,
                        jerk ? body_pos_ws : nullptr, frame_terms);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    PARC_CHECK_LAUNCH();
     hipLaunchKernelGGL(motion_score_fold_kernel, dim3(B), dim3(kFoldThreads), 0, (hipStream_t)stream, F, model.num_bodies, num_frames, frame_terms,
                        body_pos_ws, w_contact, w_pen, dt, max_jerk, losses, jerk);
-    e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_score_abi(void) { return 1; }

@@ -5,6 +5,7 @@
 
 #include <mutex>
 
+#include "parc_launch.h"
 #include "parc_sim_bpl.h"
 #include "parc_sim_core.h"
 #include "../../include/parc_sim.h"
@@ -154,12 +155,6 @@ __global__ __launch_bounds__(64) void sim_refresh_bpl_kernel(const parc_sim_mode
 
 static_assert(PARC_SIM_MAX_BODIES <= BPL_G, "one body per lane: a 16-lane group holds one env");
 
-// PARC_OK, or the error of the launch just issued
-static int launch_rc() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
-}
-
 // The argument rules that the step entry points share, checked before any HIP call
 static bool step_args_ok(const StepArgs &a, int mode) {
     if (!a.model || a.n_envs < 0 || a.n_sub <= 0 || !(a.h > 0.f) || !a.terrain.hf) return false;
@@ -186,7 +181,8 @@ static int launch_step(void *stream, const StepArgs &a, int mode, bool table) {
         else
             launch(sim_step_bpl_ctl_kernel<MODE>, a.hold, a.dof_torque);
     });
-    return launch_rc();
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_sim_step(void *stream, const parc_sim_model_t *model, parc_terrain_t terrain, int n_envs, float *root_state,
@@ -238,8 +234,7 @@ extern "C" int parc_sim_env_params_check(void *stream, const parc_sim_env_params
     }
     *g_check_cell = 0;
     hipLaunchKernelGGL(phys_check_kernel, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, env_params, n_envs, g_check_cell);
-    const int rc = launch_rc();
-    if (rc != PARC_OK) return rc;
+    PARC_CHECK_LAUNCH();
     const hipError_t e1 = hipStreamSynchronize((hipStream_t)stream);
     if (e1 != hipSuccess) return (int)e1;
     return *g_check_cell ? PARC_EINVAL : PARC_OK;
@@ -374,7 +369,8 @@ extern "C" int parc_phys_rand(void *stream, int n_envs, const int32_t *reset_mas
     if (n_envs == 0) return PARC_OK;
     hipLaunchKernelGGL(phys_rand_kernel, dim3((n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, n_envs, reset_mask, g, seed, rng_state,
                        env_params);
-    return launch_rc();
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 // the refresh of n rows: a list of envs, a mask over the envs, or neither
@@ -383,7 +379,8 @@ static int launch_refresh(void *stream, const parc_sim_model_t *model, int n, co
     if (n == 0) return PARC_OK;
     hipLaunchKernelGGL(sim_refresh_bpl_kernel, dim3((n + BPL_EPB - 1) / BPL_EPB), dim3(64), 0, (hipStream_t)stream, model, n, env_ids, mask,
                        root_state, dof_state, rigid_body_state, contact_forces);
-    return launch_rc();
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_sim_refresh_bodies(void *stream, const parc_sim_model_t *model, int n_envs, const int64_t *env_ids, int n_sel,

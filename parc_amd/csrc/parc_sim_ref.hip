@@ -7,6 +7,7 @@
 // product kernels are not held back by it.
 #include <hip/hip_runtime.h>
 
+#include "parc_launch.h"
 #include "parc_sim_core.h"
 #include "../../include/parc_sim.h"
 
@@ -38,6 +39,6 @@ extern "C" int parc_diag_sim_step_env_per_lane(void *stream, const parc_sim_mode
     if (n_envs == 0) return PARC_OK;
     hipLaunchKernelGGL(sim_step_kernel, dim3((n_envs + threads - 1) / threads), dim3(threads), 0, (hipStream_t)stream, model, terrain, n_envs,
                        root_state, dof_state, rigid_body_state, contact_forces, env_offsets, action, action_low, action_high, n_substeps, h);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/parc_hip.h"
+#include "parc_launch.h"
 #include "parc_sdf_core.h"      // column_sd, hf_window_min
 
 #define SDF_THREADS 64
@@ -89,8 +90,8 @@ extern "C" int parc_points_hf_sdf_grad(void *stream, int batch, int n_points, in
     if (!points || !hf || !min_box_center || !x_points || !y_points || !cell || !g_out || !g_points) return PARC_EINVAL;
     hipLaunchKernelGGL(points_hf_sdf_grad_kernel, dim3((n_points + SDF_THREADS - 1) / SDF_THREADS, batch), dim3(SDF_THREADS), 0, (hipStream_t)stream,
                        n_points, dim_x, dim_y, points, hf, min_box_center, x_points, y_points, half_x, half_y, base_z, inverted, cell, g_out, g_points);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }
 
 extern "C" int parc_points_hf_sdf(void *stream, int batch, int n_points, int dim_x, int dim_y, const float *points, const float *hf,
@@ -102,6 +103,6 @@ extern "C" int parc_points_hf_sdf(void *stream, int batch, int n_points, int dim
     if (!points || !hf || !min_box_center || !x_points || !y_points || !out) return PARC_EINVAL;
     hipLaunchKernelGGL(points_hf_sdf_kernel, dim3((n_points + SDF_THREADS - 1) / SDF_THREADS, batch), dim3(SDF_THREADS), 0, (hipStream_t)stream,
                        n_points, dim_x, dim_y, points, hf, min_box_center, x_points, y_points, half_x, half_y, base_z, inverted, radius, out, out_cell);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PARC_OK : (int)e;
+    PARC_CHECK_LAUNCH();
+    return PARC_OK;
 }

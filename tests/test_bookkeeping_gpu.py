@@ -1,6 +1,6 @@
-"""Exact edge-case tests of the per-step bookkeeping in parc_kin.hip whose results are integers or bit copies - which clip, tile,
-frame and grid cell an env sees: the device reset sampler (parc_reset_sample_apply), the time -> frame-pair lookup (make_query, through
-parc_calc_motion_frame) and the stand-alone heightmap rows (parc_refresh_ray_obs_hfs / parc_refresh_obs_hfs).  Every test calls the C
+"""Exact edge-case tests of the per-step bookkeeping whose results are integers or bit copies - which clip, tile, frame and grid cell an env
+sees: the device reset sampler (parc_reset_sample_apply, parc_kin.hip), the time -> frame-pair lookup (make_query of parc_motion_query.h,
+through parc_calc_motion_frame) and the stand-alone heightmap rows (parc_refresh_ray_obs_hfs / parc_refresh_obs_hfs, parc_hfgather.hip).  Every test calls the C
 ABI through parc_amd._hip and compares with the numpy references of tests/tools/bookkeeping_ref.py (pinned on the fixtures by
 tests/test_bookkeeping_ref_cpu.py).  An error in this code moves no value by 1e-5: it picks another row, so the comparisons are
 exact wherever the operation is."""

@@ -792,6 +792,18 @@ def test_library_is_built_from_the_sources_beside_it():
             _hip.OPT_LEVEL["parc_terrain.hip"] = old
 
 
+def test_every_source_is_built_with_its_flags():
+    """A .hip file left out of the build, or one of the files measured without the SLP vectoriser silently built at the default -O3,
+    would change the product without any other test failing."""
+    import os
+    from parc_amd import _hip
+    on_disk = {f for f in os.listdir(_hip.CSRC) if f.endswith(".hip")}
+    assert on_disk == set(_hip.DIAG_SOURCES) and len(_hip.DIAG_SOURCES) == len(on_disk)
+    assert set(_hip.SOURCES) == set(_hip.DIAG_SOURCES) - {"parc_sim_ref.hip"} and len(_hip.SOURCES) == len(_hip.DIAG_SOURCES) - 1
+    for f in ("parc_kin.hip", "parc_hfgather.hip", "parc_motion.hip", "parc_pose_opt.hip", "parc_returns.hip", "parc_sim.hip"):
+        assert "-fno-slp-vectorize" in _hip.OPT_LEVEL[f].split(), f
+
+
 def test_torch_util_matches_reference_fixture():
     """parc_amd/util/torch_util.py (served as util.torch_util) against fixture G1 (reference util/torch_util.py on CPU)."""
     from parc_amd.util import torch_util as tu

@@ -1,6 +1,6 @@
-"""Plain numpy references for the per-step bookkeeping of parc_kin.hip whose results are integers or exact copies: the time ->
-frame-pair lookup (make_query), the cumulative clip weights and their inversion (parc_reset_sample_apply) and the heightmap rows
-(parc_refresh_ray_obs_hfs / parc_refresh_obs_hfs).  No GPU, no torch.  tests/test_bookkeeping_ref_cpu.py pins these functions on the
+"""Plain numpy references for the per-step bookkeeping whose results are integers or exact copies: the time -> frame-pair lookup (make_query,
+parc_motion_query.h), the cumulative clip weights and their inversion (parc_reset_sample_apply, parc_kin.hip) and the heightmap rows
+(parc_refresh_ray_obs_hfs / parc_refresh_obs_hfs, parc_hfgather.hip).  No GPU, no torch.  tests/test_bookkeeping_ref_cpu.py pins these functions on the
 fixtures, tests/test_bookkeeping_gpu.py compares the kernels with them."""
 import numpy as np
 
