@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libparc_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip", "parc_moopt.hip",
+SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_rollout.hip", "parc_optim.hip", "parc_colreduce.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip", "parc_moopt.hip",
            "parc_augment.hip", "parc_hfgather.hip", "parc_motion.hip", "parc_pose_opt.hip", "parc_returns.hip"]
 # The diagnostics library (tools/parc_diag.py; never loaded by this package): the same sources with -DPARC_DIAG_BUILD (timing-ablation bits of
 # parc_track_post_step, the heightmap kernel's measurement knobs) plus the one-env-per-lane reference formulation of the simulator.

@@ -266,7 +266,7 @@ extern "C" int parc_sim_step_phys(void *stream, const parc_sim_model_t *model, p
 // =============================================================================================
 // Device-side sampler of the per-env table (parc_phys_rand): one thread per env, Philox4x32-10 keyed by the seed with counter
 // (env, block, launch counter lo, hi) - block 0 / 1: the eight fields of a reset, block 2: a push, block 3: the interval after a reset.
-// state[0] = launch counter, state[1] = ticket of the launch's last workgroup (the scheme of rng_step_kernel, parc_ppo.hip).
+// state[0] = launch counter, state[1] = ticket of the launch's last workgroup (the scheme of rng_step_kernel, parc_rollout.hip).
 // =============================================================================================
 __device__ __forceinline__ void phys_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
 #pragma unroll

@@ -254,6 +254,68 @@ def test_relu_bwd_bias_grad_kernel():
         _hip.check(L.parc_weighted_colsum(_hip.stream(), rows, dim, _hip.ptr(x), _hip.ptr(w), _hip.ptr(out), _hip.ptr(ws)), "weighted_colsum")
         ref = (w.double().unsqueeze(0) @ x.double()).squeeze(0)
         assert float((out.double() - ref).abs().max()) <= 2e-5 * (rows ** 0.5)
+    # both at the edges of the column-chunk skeleton, exactly (COL_CHUNK_EDGES)
+    for rows, dim in COL_CHUNK_EDGES:
+        gy, y, w = _ints(g, rows, dim), _ints(g, rows, dim), _ints(g, rows)
+        ref = torch.where(y <= 0, torch.zeros_like(gy), gy)
+        ws = torch.empty(int(L.parc_relu_bwd_workspace_floats(rows, dim)), device=DEV)
+        gy_d, y_d, db = _with_tail(gy), y.to(DEV), _with_tail(torch.full((dim,), 3.0))
+        _hip.check(L.parc_relu_bwd_bias_grad(_hip.stream(), rows, dim, _hip.ptr(gy_d), _hip.ptr(y_d), _hip.ptr(db), _hip.ptr(ws)), "relu_bwd")
+        assert torch.equal(gy_d.cpu(), _expect(ref)), (rows, dim)
+        assert torch.equal(db.cpu(), _expect(ref.long().sum(0))), (rows, dim)
+        w_d, out = w.to(DEV), _with_tail(torch.full((dim,), -1.0))
+        _hip.check(L.parc_weighted_colsum(_hip.stream(), rows, dim, _hip.ptr(y_d), _hip.ptr(w_d), _hip.ptr(out), _hip.ptr(ws)), "weighted_colsum")
+        assert torch.equal(out.cpu(), _expect((w.long().unsqueeze(1) * y.long()).sum(0))), (rows, dim)
+
+
+# The column-chunk skeleton (parc_colreduce.hip): 64 float4 lanes = 256 columns per column block, 4 row groups, chunks of 64 rows (moments,
+# ingest) or 128 rows (ReLU backward, weighted column sum).  Rows and columns on both sides of each of these edges.  The inputs are
+# integer-valued floats in [-4, 4]: every sum, sum of squares and weighted sum stays below 2^24 and is exact in fp32 in any order, so the
+# results must EQUAL the int64 sums of the CPU.  Every output is 4 floats longer than it needs to be and keeps a sentinel there.
+COL_CHUNK_EDGES = [(rows, dim) for rows in (1, 3, 4, 5, 64, 65, 128, 129, 257) for dim in (4, 252, 256, 260)]
+_TAIL = 77.0
+
+
+def _ints(g, *shape):
+    return torch.randint(-4, 5, shape, generator=g).float()
+
+
+def _with_tail(t):
+    """t on the device, flat, followed by 4 sentinel floats"""
+    return torch.cat([t.reshape(-1).float(), torch.full((4,), _TAIL)]).to(DEV)
+
+
+def _expect(t):
+    return torch.cat([t.reshape(-1).float(), torch.full((4,), _TAIL)])
+
+
+def test_moments_and_obs_ingest_at_the_column_chunk_edges():
+    """parc_moments_accumulate and parc_obs_ingest (normalise + buffer copy + moments) on COL_CHUNK_EDGES, exactly.  Mean 0, std 1 and a
+    clip above 4: the normalised rows and the copied buffer row equal x."""
+    from parc_amd import _hip
+    L = _hip.lib()
+    g = torch.Generator().manual_seed(3)
+    T, row = 3, 1
+    for rows, dim in COL_CHUNK_EDGES:
+        x, acc0 = _ints(g, rows, dim), _ints(g, 2, dim)
+        xl = x.long()
+        acc_ref = _expect(acc0.long() + torch.stack([xl.sum(0), (xl * xl).sum(0)]))
+        x_d = x.to(DEV)
+        ws = torch.empty(int(L.parc_moments_workspace_floats(rows, dim)), device=DEV)
+        acc = _with_tail(acc0)
+        _hip.check(L.parc_moments_accumulate(_hip.stream(), rows, dim, _hip.ptr(x_d), _hip.ptr(acc), _hip.ptr(ws)), "moments_accumulate")
+        assert torch.equal(acc.cpu(), acc_ref), (rows, dim)
+        acc, norm = _with_tail(acc0), _with_tail(torch.full((rows, dim), 9.0))
+        buf = _with_tail(torch.full((T, rows, dim), 9.0))
+        mean, std = torch.zeros(dim, device=DEV), torch.ones(dim, device=DEV)
+        head = torch.tensor([row], dtype=torch.int64, device=DEV)
+        _hip.check(L.parc_obs_ingest(_hip.stream(), rows, dim, _hip.ptr(x_d), _hip.ptr(mean), _hip.ptr(std), 5.0, _hip.ptr(norm), _hip.ptr(buf),
+                                     _hip.ptr(head), _hip.ptr(acc), _hip.ptr(ws)), "obs_ingest")
+        buf_ref = torch.full((T, rows, dim), 9.0)
+        buf_ref[row] = x
+        assert torch.equal(norm.cpu(), _expect(x)), (rows, dim)
+        assert torch.equal(buf.cpu(), _expect(buf_ref)), (rows, dim)
+        assert torch.equal(acc.cpu(), acc_ref), (rows, dim)
 
 
 def test_flat_sgd_step_equals_torch_sgd_with_clipping():
