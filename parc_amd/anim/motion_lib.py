@@ -109,6 +109,7 @@ class MotionLib:
         B = self._kin_char_model.get_num_joints()
         clips = []
         self._motion_files, self._motion_names, self._terrains, self._motion_extras = [], [], [], []
+        self._hf_mask_inds = []          # per motion: the per-frame [k, 2] int64 cell lists of the file, or None (reference :335-344)
         for path, w in zip(files, weights):
             data, ter = self._load_one(path)
             fps = data.get("fps", 30)
@@ -137,6 +138,10 @@ class MotionLib:
                 ter.update_old()
                 ter.to_torch(self._device)
             self._terrains.append(ter)
+            inds = data.get("hf_mask_inds")
+            if inds is not None:
+                inds = [torch.as_tensor(i if isinstance(i, torch.Tensor) else np.asarray(i), dtype=torch.int64).to(device=self._device) for i in inds]
+            self._hf_mask_inds.append(inds)
             clips.append(dict(frames=frames, contacts=con, fps=float(fps), loop=LoopMode[loop].value, weight=float(w)))
         return clips
 
