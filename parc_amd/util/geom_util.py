@@ -138,6 +138,38 @@ def get_char_point_samples(char_model, sphere_num_subdivisions=0, box_num_slices
     return out
 
 
+def get_minimal_char_point_samples(char_model):
+    """-> list over bodies of [P_b, 3] float32 tensors on the model's device: the sphere's centre, two points per capsule (a third of
+    its length either side of its centre, on its axis), the eight corners of a box.  The generator's terrain-penetration loss uses
+    these (reference util/geom_util.py:873)."""
+    from ..anim.kin_char_model import GeomType
+    target_device = char_model._device
+    device = "cpu"          # built on the host, like get_char_point_samples
+    f32 = lambda a: torch.as_tensor(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a), dtype=torch.float32, device=device)
+    out = []
+    for b in range(char_model.get_num_joints()):
+        body = []
+        for g in char_model.get_geoms(b):
+            if g._shape_type == GeomType.SPHERE:
+                body.append(f32(g._offset).reshape(1, 3).clone())
+            elif g._shape_type == GeomType.CAPSULE:
+                span = f32(g._dims)
+                centre = f32(g._offset) + span / 2.0
+                zax = torch.tensor([0.0, 0.0, 1.0], device=device)
+                axis = torch.linalg.cross(zax, span)
+                axis = zax if torch.linalg.vector_norm(axis) < 1e-5 else axis / torch.linalg.vector_norm(axis)
+                angle = torch.acos(torch.dot(axis, span))          # as the reference has it (see get_char_point_samples)
+                h = torch.linalg.vector_norm(span).item()
+                pts = torch.tensor([[0.0, 0.0, h / 3.0], [0.0, 0.0, -h / 3.0]], dtype=torch.float32, device=device)
+                body.append(_rotate_by_axis_angle(axis, angle, pts) + centre)
+            elif g._shape_type == GeomType.BOX:
+                body.append(get_box_point_surface_samples(f32(g._dims), device, num_slices=2, dim_x=2, dim_y=2) + f32(g._offset))
+            else:
+                raise AssertionError(g._shape_type)
+        out.append((torch.cat(body, dim=0) if body else torch.zeros((0, 3), dtype=torch.float32, device=device)).to(target_device))
+    return out
+
+
 def sdSphere(p, c, r):
     """signed distance of points p to the sphere of centre c and radius r (reference util/geom_util.py:167-171)"""
     return torch.linalg.vector_norm(p - c, dim=-1) - r
