@@ -145,11 +145,63 @@ class TtCase:
                 j = a[1:] - a[:-1]
                 jn = np.linalg.norm(j, axis=-1)
                 sums[2, m] = np.clip(jn - self.lim, 0.0, None).sum()
-                d = np.where((jn > self.lim)[..., None], w2 * j / np.maximum(jn, 1e-300)[..., None], 0.0)
+                # torch's clamp(min=0) passes the gradient where its argument equals the bound, and the norm's at j = 0 is 0
+                d = np.where(((jn >= self.lim) & (jn > 0.0))[..., None], w2 * j / np.maximum(jn, 1e-300)[..., None], 0.0)
                 for off, coef in ((0, -1.0), (1, 3.0), (2, -3.0), (3, 1.0)):
                     gp[off:off + T - 3] += coef * d
             g_pos[s:s + T] = gp
         return sums, g_pos, g_r
+
+    def jerk_gaps(self):
+        """float64 | |third difference| - limit | of every (frame, body) that has one, all motions in one array"""
+        gaps = []
+        for m, T in enumerate(self.lengths):
+            if T >= 4:
+                p = self.pos[int(self.ss[m]):int(self.ss[m]) + T].astype(np.float64)
+                j = p[3:] - 3.0 * p[2:-1] + 3.0 * p[1:-2] - p[:-3]
+                gaps.append(np.abs(np.linalg.norm(j, axis=-1) - self.lim).reshape(-1))
+        return np.concatenate(gaps) if gaps else np.zeros(0)
+
+
+# The designed cases of the frame-to-frame terms (fixture G34 records the reference's expressions on them): every length at which a
+# term first exists, one and many bodies, more than one workgroup, both sides of the jerk kink and the kink itself, empty masks, seams.
+DESIGNED_TT = tuple("t{}b{}".format(T, B) for B in (1, 15) for T in (1, 2, 3, 4, 5)) + ("n270", "kink", "zero", "keep0", "pc0", "seams")
+
+
+def designed_tt(name):
+    """-> TtCase.  Outside the frames placed on the kink, | |j| - limit | >= 1e-4 in float64 (jerk_gaps; tests/test_pose_opt_ref_cpu.py
+    asserts it)."""
+    seed = 3400 + DESIGNED_TT.index(name)
+    if name[0] == "t":
+        T, B = name[1:].split("b")
+        return TtCase((int(T),), int(B), seed)
+    if name == "n270":
+        return TtCase((18,), 15, seed)                      # 270 threads: crosses one workgroup of 256
+    if name == "seams":
+        return TtCase((1, 2, 3, 4, 20), 15, seed)            # seams at frames 1, 3, 6 and 10, all inside the first workgroup (17 frames)
+    if name in ("keep0", "pc0"):
+        case = TtCase((9, 4), 3, seed)
+        if name == "keep0":
+            case.keep[:] = 0.0
+        else:
+            case.pc[:] = 0.0
+        return case
+    rng = np.random.default_rng(seed)
+    if name == "kink":
+        # positions on a grid of quarters: every third difference, its square and 2.5 = |(1.5, 2, 0)| are exact in fp32 and in float64
+        case = TtCase((6, 5), 2, seed)
+        case.pos = f32(rng.integers(-8, 9, size=case.pos.shape) / 4.0)
+        case.lim = 2.5
+        for f0, b, j in ((0, 0, (1.5, 2.0, 0.0)), (7, 1, (-2.0, 0.0, 1.5))):        # the second one in the motion behind the seam
+            case.pos[f0 + 1:f0 + 3, b] = case.pos[f0, b]
+            case.pos[f0 + 3, b] = case.pos[f0, b] + f32(j)
+        return case
+    assert name == "zero", name
+    # |j| = 0 with limit 0: body 0 moves at a constant (exactly representable) velocity
+    case = TtCase((7,), 3, seed)
+    case.lim = 0.0
+    case.pos[:, 0] = f32([0.5, -0.25, 1.0]) + np.arange(7, dtype=np.float32)[:, None] * f32([0.25, 0.5, -0.125])
+    return case
 
 
 # ---------------------------------------------------------------------------------------------------------- ragged terrain query
