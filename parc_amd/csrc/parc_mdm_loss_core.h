@@ -281,13 +281,17 @@ PARC_ML_FN int point_owner(const layout &L, const int32_t *start, int p) {
 }
 
 // signed distance of sample point p of frame f to the sample's terrain (negative inside the ground) and the column that attains it
-PARC_ML_FN void point_item(const parc_mdm_loss_cfg_t &c, const layout &L, const sample &s, int f, int p) {
+PARC_ML_FN float point_sdf(const parc_mdm_loss_cfg_t &c, const layout &L, const sample &s, int f, int p, int &cell) {
     const int b = point_owner(L, s.point_start, p);
     const v3 w = ld3(s.scr + L.o_bpos[0] + ((size_t)f * L.nb + b) * 3) + qrot(ld4(s.scr + L.o_brot[0] + ((size_t)f * L.nb + b) * 4), ld3(s.points + (size_t)p * 3));
-    int cell = 0;
+    cell = 0;
     float sd = hf_window_min(w.x, w.y, w.z, s.scr + L.o_hf, c.dim_x, c.dim_y, c.ox, c.oy, s.grid_x, s.grid_y, c.half_x, c.half_y, c.base_z, 1, cell);
     if (!(w.x == w.x && w.y == w.y && w.z == w.z)) sd = __builtin_nanf("");      // torch's abs / clamp / min propagate a NaN coordinate
-    s.scr[L.o_psdf + f * L.P + p] = -sd;
+    return -sd;
+}
+PARC_ML_FN void point_item(const parc_mdm_loss_cfg_t &c, const layout &L, const sample &s, int f, int p) {
+    int cell;
+    s.scr[L.o_psdf + f * L.P + p] = point_sdf(c, L, s, f, p, cell);
     reinterpret_cast<int32_t *>(s.scr + L.o_pcell)[f * L.P + p] = cell;
 }
 
@@ -564,10 +568,10 @@ PARC_ML_FN sample make_sample(const parc_char_model_t &m, const parc_mdm_loss_cf
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Argument rules of the entry points (include/parc_mdm_loss.h), answered before any HIP call
 // ---------------------------------------------------------------------------------------------------------------------------------
-static inline int check_cfg(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, int B) {
+// the counts, the model and the feature layout (shared with the guidance step, parc_mdm_guide_core.h)
+static inline int check_layout(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, int B) {
     if (B < 0 || m.num_bodies < 1 || m.num_bodies > PARC_MAX_BODIES || m.dof_size < 0 || m.dof_size > PARC_MAX_DOFS) return PARC_EINVAL;
-    if (c.seq_len < 1 || c.ref_idx < 0 || c.ref_idx >= c.seq_len || c.dim_x < 1 || c.dim_y < 1 || c.num_points < 0) return PARC_EINVAL;
-    if (c.loss_fn != PARC_MDM_LOSS_SQUARED_L2 && c.loss_fn != PARC_MDM_LOSS_PSEUDO_HUBER) return PARC_EINVAL;
+    if (c.seq_len < 1 || c.dim_x < 1 || c.dim_y < 1 || c.num_points < 0) return PARC_EINVAL;
     for (int b = 1; b < m.num_bodies; ++b) {
         if (m.parent[b] < 0 || m.parent[b] >= b) return PARC_EINVAL;
         const int n = m.joint_type[b] == PARC_JOINT_HINGE ? 1 : m.joint_type[b] == PARC_JOINT_SPHERICAL ? 3 : 0;
@@ -585,6 +589,13 @@ static inline int check_cfg(const parc_char_model_t &m, const parc_mdm_loss_cfg_
         for (int i = 0; i < k; ++i)          // disjoint, and their lengths add up to D: a tiling
             if (off[i] >= 0 && len[i] > 0 && len[k] > 0 && off[i] < off[k] + len[k] && off[k] < off[i] + len[i]) return PARC_EINVAL;
     }
+    return PARC_OK;
+}
+
+static inline int check_cfg(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, int B) {
+    if (check_layout(m, c, B) != PARC_OK) return PARC_EINVAL;
+    if (c.ref_idx < 0 || c.ref_idx >= c.seq_len) return PARC_EINVAL;
+    if (c.loss_fn != PARC_MDM_LOSS_SQUARED_L2 && c.loss_fn != PARC_MDM_LOSS_PSEUDO_HUBER) return PARC_EINVAL;
     if (c.off_joint_pos < 0 && (c.enabled & ((1 << PARC_MDM_LOSS_SIMPLE_BODY_POS) | (1 << PARC_MDM_LOSS_BODY_POS_CONSISTENCY)))) return PARC_EINVAL;
     if (c.off_contacts < 0 && (c.enabled & (1 << PARC_MDM_LOSS_SIMPLE_CONTACT))) return PARC_EINVAL;
     // sizes in 64 bits before the layout multiplies them as int
