@@ -15,7 +15,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libparc_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["parc_kin.hip", "parc_sim.hip", "parc_ppo.hip", "parc_rollout.hip", "parc_optim.hip", "parc_colreduce.hip", "parc_terrain.hip", "parc_render.hip", "parc_score.hip", "parc_netstats.hip", "parc_moopt.hip",
-           "parc_augment.hip", "parc_mdm_batch.hip", "parc_mdm_loss.hip", "parc_mdm_guide.hip", "parc_hfgather.hip", "parc_motion.hip", "parc_pose_opt.hip", "parc_returns.hip"]
+           "parc_augment.hip", "parc_mdm_batch.hip", "parc_mdm_loss.hip", "parc_mdm_guide.hip", "parc_mdm_gen.hip", "parc_hfgather.hip", "parc_motion.hip", "parc_pose_opt.hip", "parc_returns.hip"]
 # The diagnostics library (tools/parc_diag.py; never loaded by this package): the same sources with -DPARC_DIAG_BUILD (timing-ablation bits of
 # parc_track_post_step, the heightmap kernel's measurement knobs) plus the one-env-per-lane reference formulation of the simulator.
 DIAG_LIB_PATH = os.path.join(LIB_DIR, "libparc_hip_diag.so")
@@ -118,7 +118,9 @@ OPT_LEVEL = {"parc_kin.hip": os.environ.get("PARC_KIN_OPT", NO_SLP), "parc_sim.h
              # the generator's loss too (parc_mdm_loss_core.h)
              "parc_mdm_loss.hip": "-O3 -ffp-contract=off",
              # and the guidance step, which calls the loss's primitives (parc_mdm_guide_core.h)
-             "parc_mdm_guide.hip": "-O3 -ffp-contract=off"}
+             "parc_mdm_guide.hip": "-O3 -ffp-contract=off",
+             # and the generator call around the sampling loop (parc_mdm_gen_core.h)
+             "parc_mdm_gen.hip": "-O3 -ffp-contract=off"}
 
 
 DIGEST_PATH = os.path.join(LIB_DIR, "libparc_hip.digest")
@@ -302,6 +304,9 @@ def _declare(L):
     if hasattr(L, "parc_mdm_guide_abi"):
         from . import _hip_mdm_guide
         _hip_mdm_guide.declare(L)
+    if hasattr(L, "parc_mdm_gen_abi"):
+        from . import _hip_mdm_gen
+        _hip_mdm_gen.declare(L)
 
 
 EXPORTED = ["parc_abi_version", "parc_refresh_ray_obs_hfs", "parc_refresh_obs_hfs", "parc_dof_to_rot", "parc_rot_to_dof",
@@ -319,7 +324,8 @@ EXPORTED = ["parc_abi_version", "parc_refresh_ray_obs_hfs", "parc_refresh_obs_hf
             "parc_augment_frames", "parc_augment_terrains", "parc_augment_localize", "parc_augment_abi",
             "parc_mdm_heightfields", "parc_mdm_windows", "parc_mdm_batch_abi",
             "parc_mdm_loss_forward", "parc_mdm_loss_backward", "parc_mdm_loss_lds_bytes", "parc_mdm_loss_abi",
-            "parc_mdm_guide_step", "parc_mdm_guide_lds_bytes", "parc_mdm_guide_abi"]
+            "parc_mdm_guide_step", "parc_mdm_guide_lds_bytes", "parc_mdm_guide_abi",
+            "parc_mdm_gen_encode", "parc_mdm_gen_decode", "parc_mdm_gen_abi"]
 
 
 def check(rc, what):

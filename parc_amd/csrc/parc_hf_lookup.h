@@ -1,19 +1,12 @@
-// Heightfield cell lookup and the per-env affine maps of the heightmap gather, shared by the stand-alone gather (parc_hfgather.hip)
-// and the tracker step's heightmap wave and height termination (parc_kin.hip).  Device only.
+// Heightfield cell lookup (hf_lookup: parc_hf_cell.h, which the host builds read too) and the per-env affine maps of the heightmap
+// gather, shared by the stand-alone gather (parc_hfgather.hip) and the tracker step's heightmap wave and height termination
+// (parc_kin.hip).  Device only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/parc_hip.h"
+#include "parc_hf_cell.h"
 #include "parc_math.h"
-
-// util/terrain_util.py:107-126: torch.round (half to even) then clamp to the grid
-PARC_DEV float hf_lookup(const parc_terrain_t &t, float px, float py) {
-    float fi = rintf((px - t.min_x) / t.dx);
-    float fj = rintf((py - t.min_y) / t.dy);
-    fi = fminf(fmaxf(fi, 0.f), (float)(t.dim_x - 1));
-    fj = fminf(fmaxf(fj, 0.f), (float)(t.dim_y - 1));
-    return t.hf[(int)fi * t.dim_y + (int)fj];
-}
 
 struct hf_env_prm {
     float ax, bx, cx, ay, by, cy, gz;

@@ -245,6 +245,15 @@ PARC_ML_FN v3 ang_vel(q4 q0, q4 q1, float dt) {
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Forward phases
 // ---------------------------------------------------------------------------------------------------------------------------------
+// The rotation of joint b >= 1 of J in frame f of one side (0 = predicted, from the dofs in x; 1 = true, from the quaternions)
+PARC_ML_FN q4 joint_quat(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, const sample &s, int side, int f, int b, int J) {
+    if (side != 0) return ld4(s.joint_rot + ((size_t)f * J + (b - 1)) * 4);
+    const int jt = m.joint_type[b], d0 = c.off_joint_rot + m.dof_idx[b];
+    if (jt == PARC_JOINT_HINGE) return aa_to_quat(joint_axis(m, b), feat(s, c, f, d0));
+    if (jt == PARC_JOINT_SPHERICAL) return em_to_quat(feat3(s, c, f, d0));
+    return q4{0.f, 0.f, 0.f, 1.f};
+}
+
 // The chain of one frame of one side (0 = predicted, from x; 1 = true, from the quaternions) into the scratch
 PARC_ML_FN void chain_item(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, const layout &L, const sample &s, int side, int f) {
     float *bpos = s.scr + L.o_bpos[side] + (size_t)f * L.nb * 3, *brot = s.scr + L.o_brot[side] + (size_t)f * L.nb * 4;
@@ -257,15 +266,7 @@ PARC_ML_FN void chain_item(const parc_char_model_t &m, const parc_mdm_loss_cfg_t
         st4(brot, ld4(s.root_rot + (size_t)f * 4));
     }
     for (int b = 1; b < L.nb; ++b) {
-        q4 j;
-        if (side == 0) {
-            const int jt = m.joint_type[b], d0 = c.off_joint_rot + m.dof_idx[b];
-            if (jt == PARC_JOINT_HINGE) j = aa_to_quat(joint_axis(m, b), feat(s, c, f, d0));
-            else if (jt == PARC_JOINT_SPHERICAL) j = em_to_quat(feat3(s, c, f, d0));
-            else j = q4{0.f, 0.f, 0.f, 1.f};
-        } else {
-            j = ld4(s.joint_rot + ((size_t)f * L.J + (b - 1)) * 4);
-        }
+        const q4 j = joint_quat(m, c, s, side, f, b, L.J);
         st4(jq + (b - 1) * 4, j);
         const int p = m.parent[b];
         const q4 rp = ld4(brot + p * 4);
@@ -569,27 +570,38 @@ PARC_ML_FN sample make_sample(const parc_char_model_t &m, const parc_mdm_loss_cf
 // Argument rules of the entry points (include/parc_mdm_loss.h), answered before any HIP call
 // ---------------------------------------------------------------------------------------------------------------------------------
 // the counts, the model and the feature layout (shared with the guidance step, parc_mdm_guide_core.h)
-static inline int check_layout(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, int B) {
-    if (B < 0 || m.num_bodies < 1 || m.num_bodies > PARC_MAX_BODIES || m.dof_size < 0 || m.dof_size > PARC_MAX_DOFS) return PARC_EINVAL;
-    if (c.seq_len < 1 || c.dim_x < 1 || c.dim_y < 1 || c.num_points < 0) return PARC_EINVAL;
+// a model the chain can walk: bodies stored parents-first, every joint's dofs inside [0, dof_size)
+static inline int check_model(const parc_char_model_t &m) {
+    if (m.num_bodies < 1 || m.num_bodies > PARC_MAX_BODIES || m.dof_size < 0 || m.dof_size > PARC_MAX_DOFS) return PARC_EINVAL;
     for (int b = 1; b < m.num_bodies; ++b) {
         if (m.parent[b] < 0 || m.parent[b] >= b) return PARC_EINVAL;
         const int n = m.joint_type[b] == PARC_JOINT_HINGE ? 1 : m.joint_type[b] == PARC_JOINT_SPHERICAL ? 3 : 0;
         if (n && (m.dof_idx[b] < 0 || m.dof_idx[b] + n > m.dof_size)) return PARC_EINVAL;
     }
-    // the slices tile [0, D): every column of g_x is written
-    const int J = m.num_bodies - 1;
-    int want = 6 + m.dof_size + (c.off_joint_pos >= 0 ? 3 * J : 0) + (c.off_contacts >= 0 ? m.num_bodies : 0);
-    if (c.feat_dim != want) return PARC_EINVAL;
-    const int off[5] = {c.off_root_pos, c.off_root_rot, c.off_joint_rot, c.off_joint_pos, c.off_contacts};
-    const int len[5] = {3, 3, m.dof_size, 3 * J, m.num_bodies};
+    return PARC_OK;
+}
+
+// the slices {root_pos, root_rot, joint_rot, joint_pos, contacts} of lengths len[] tile [0, feat_dim); the last two may be absent (< 0)
+static inline int check_tiling(int feat_dim, const int off[5], const int len[5]) {
+    int want = len[0] + len[1] + len[2] + (off[3] >= 0 ? len[3] : 0) + (off[4] >= 0 ? len[4] : 0);
+    if (feat_dim != want) return PARC_EINVAL;
     for (int k = 0; k < 5; ++k) {
         if (k >= 3 && off[k] < 0) continue;
-        if (off[k] < 0 || off[k] + len[k] > c.feat_dim) return PARC_EINVAL;
+        if (off[k] < 0 || off[k] + len[k] > feat_dim) return PARC_EINVAL;
         for (int i = 0; i < k; ++i)          // disjoint, and their lengths add up to D: a tiling
             if (off[i] >= 0 && len[i] > 0 && len[k] > 0 && off[i] < off[k] + len[k] && off[k] < off[i] + len[i]) return PARC_EINVAL;
     }
     return PARC_OK;
+}
+
+static inline int check_layout(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, int B) {
+    if (B < 0 || check_model(m) != PARC_OK) return PARC_EINVAL;
+    if (c.seq_len < 1 || c.dim_x < 1 || c.dim_y < 1 || c.num_points < 0) return PARC_EINVAL;
+    // the slices tile [0, D): every column of g_x is written
+    const int J = m.num_bodies - 1;
+    const int off[5] = {c.off_root_pos, c.off_root_rot, c.off_joint_rot, c.off_joint_pos, c.off_contacts};
+    const int len[5] = {3, 3, m.dof_size, 3 * J, m.num_bodies};
+    return check_tiling(c.feat_dim, off, len);
 }
 
 static inline int check_cfg(const parc_char_model_t &m, const parc_mdm_loss_cfg_t &c, int B) {

@@ -37,6 +37,14 @@ class MDMKeyType(enum.Enum):
     IN_PAINT_PARAMS = 16
 
 
+class GenerationMode(enum.Enum):
+    """reference diffusion/mdm.py:57-61"""
+    MODE_REVERSE_DIFFUSION = 0
+    MODE_DDIM = 1
+    MODE_ECM = 2
+    NONE = 3
+
+
 class MDMCustomGuidance:
     """what conds[GUIDANCE_PARAMS] carries (reference diffusion/diffusion_util.py:38-57): class attributes as defaults"""
     obs_cfg_scale = None

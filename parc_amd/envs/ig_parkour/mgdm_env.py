@@ -18,8 +18,9 @@ How it sits on the MI355X path:
 
 The generator is a callable ``generator(target_xy, prev_frames, terrain, char_model, settings) -> MotionFrames`` with the attributes
 the reference reads from its model object (``_num_prev_states``, ``_sequence_fps``, ``_dx/_dy/_num_x_neg/...``).  It is the ONLY entry:
-this package imports nothing of the reference's ``diffusion`` package and opens no model file; the adapter that wraps stage 1's trained
-``diffusion.mdm.MDM`` is user-side code, and ``mgdm.model_path`` without a generator is an error.
+this package imports nothing of the reference's ``diffusion`` package and opens no model file; stage 1's trained ``diffusion.mdm.MDM``
+is loaded by the user and wrapped in ``parc_amd.diffusion.gen_util.MDMGenerator``, and ``mgdm.model_path``
+without a generator is an error.
 Checked against fixture G21 (the reference's class driven on CPU with a recorded stand-in generator).
 """
 import enum
@@ -437,6 +438,15 @@ class MotionGenDeepMimicEnv:
         rp, rr, _, _, jr, _, con = self._motion_lib.calc_motion_frame(motion_ids, times)
         return MotionFrames(root_pos=rp, root_rot=rr, joint_rot=jr, contacts=con).unsqueeze(1)
 
+    def _plan_rows(self, plan):
+        """the plan as MotionLib rows [envs, frames, 6 + dofs] = root position, root exponential map, joint dofs.  A plan that carries
+        them already (`frames`, as parc_amd.diffusion.gen_util's decode writes them from the quaternions it holds) is taken as it is."""
+        rows = getattr(plan, "frames", None)
+        want = tuple(plan.root_pos.shape[0:2]) + (6 + self._kin_char_model.get_dof_size(),)
+        if torch.is_tensor(rows) and tuple(rows.shape) == want and rows.dtype == torch.float32 and rows.device == plan.root_pos.device:
+            return rows
+        return torch.cat([plan.root_pos, torch_util.quat_to_exp_map(plan.root_rot), self._kin_char_model.rot_to_dof(plan.joint_rot.contiguous())], dim=-1)
+
     # ------------------------------------------------------------------ replan (reference :575-826)
     @torch.no_grad()
     def replan(self):
@@ -473,7 +483,7 @@ class MotionGenDeepMimicEnv:
         settings.prev_state_ind_key = torch.ones(self._num_envs, dtype=torch.bool, device=dev)
         settings.prev_state_ind_key[hard_ids] = False
         plan = self._mgen(self._target_xy, prev_frames, self._terrain, self._kin_char_model, settings)
-        frames = torch.cat([plan.root_pos, torch_util.quat_to_exp_map(plan.root_rot), self._kin_char_model.rot_to_dof(plan.joint_rot.contiguous())], dim=-1)
+        frames = self._plan_rows(plan)
         if self._motion_lib is None or tuple(frames.shape[0:2]) != self._motion_lib._uniform_shape:
             self._motion_lib = motion_lib.MotionLib(frames.contiguous(), self._kin_char_model, dev, init_type="motion_frames",
                                                     loop_mode=motion_lib.LoopMode.CLAMP, fps=self._mgen._sequence_fps, contact_info=True,
