@@ -8,7 +8,7 @@
  * one launch for B samples, one workgroup of PARC_MDM_GEN_THREADS per sample (lanes stride over the grid cells and over the frames).
  * After it the standardised sample becomes world-frame motion frames: parc_mdm_gen_decode, one launch, one lane per (sample, frame).
  * The arithmetic is in parc_amd/csrc/parc_mdm_gen_core.h (quaternion functions, joint rotations and the pose chain are those of
- * parc_mdm_loss_core.h; the cell lookup is parc_hf_cell.h), compiled with floating-point contraction off for the device and the host.
+ * parc_mdm_pose_core.h; the cell lookup is parc_hf_cell.h), compiled with floating-point contraction off for the device and the host.
  * Vector stores only; no atomics; nothing is allocated, read back or waited for.  Sample b's outputs depend on sample b alone (and on
  * the terrain, mean and std, which all samples share): a NaN or Inf in its inputs reaches its outputs only.  Every terrain index is
  * clamped to the grid before its load, whatever the bits of the inputs (a NaN coordinate reads row or column 0).

@@ -8,7 +8,7 @@
  * sample by itself.  The sample's heightfield (times max_h), body transforms and cotangents live in dynamic LDS; no [points, columns]
  * tensor exists; cotangents are gathered per (frame, body), not scattered: no float atomics; vector stores only; every sum is folded in
  * a fixed order that does not depend on the launch shape, so two runs give the same bits.  The arithmetic is in
- * parc_amd/csrc/parc_mdm_guide_core.h (pose chain, its adjoint and the terrain scan are those of parc_mdm_loss_core.h), compiled with
+ * parc_amd/csrc/parc_mdm_guide_core.h (pose chain, its adjoint and the terrain scan are those of parc_mdm_pose_core.h), compiled with
  * floating-point contraction off for the device and for the host.
  *
  * Terms (rows of terms [PARC_MDM_GUIDE_TERMS, B], unweighted, in the order the reference adds them; a term switched off is written 0).

@@ -117,7 +117,7 @@ OPT_LEVEL = {"parc_kin.hip": os.environ.get("PARC_KIN_OPT", NO_SLP), "parc_sim.h
              "parc_mdm_batch.hip": "-O3 -ffp-contract=off",
              # the generator's loss too (parc_mdm_loss_core.h)
              "parc_mdm_loss.hip": "-O3 -ffp-contract=off",
-             # and the guidance step, which calls the loss's primitives (parc_mdm_guide_core.h)
+             # and the guidance step, on the same primitives (parc_mdm_guide_core.h, parc_mdm_pose_core.h)
              "parc_mdm_guide.hip": "-O3 -ffp-contract=off",
              # and the generator call around the sampling loop (parc_mdm_gen_core.h)
              "parc_mdm_gen.hip": "-O3 -ffp-contract=off"}

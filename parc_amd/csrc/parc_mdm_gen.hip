@@ -10,7 +10,7 @@
 
 using namespace parc_mgn;
 
-// One workgroup per sample; the pose chain's scratch (parc_mgn::make_layout) is the dynamic LDS.  The chain reads the canonical root
+// One workgroup per sample; the pose chain's scratch (parc_mgn::encode_pose) is the dynamic LDS.  The chain reads the canonical root
 // back from out_root_pos / out_root_rot: no __restrict__ on the outputs.
 __global__ __launch_bounds__(PARC_MDM_GEN_THREADS) void mdm_gen_encode_kernel(
     parc_char_model_t model, parc_mdm_gen_cfg_t cfg, parc_terrain_t terrain, const float *root_pos, const float *root_rot, const float *joint_rot,

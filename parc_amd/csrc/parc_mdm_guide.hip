@@ -10,7 +10,7 @@
 
 using namespace parc_mg;
 
-// One workgroup per sample; the sample's scratch (parc_mg::glayout) is the dynamic LDS.  x and x_out may be the same array: no
+// One workgroup per sample; the sample's scratch (parc_mg::layout) is the dynamic LDS.  x and x_out may be the same array: no
 // __restrict__ on either.
 __global__ __launch_bounds__(PARC_MDM_GUIDE_THREADS) void mdm_guide_step_kernel(
     parc_char_model_t model, parc_mdm_guide_cfg_t cfg, int B, const float *x, const float *__restrict__ mean, const float *__restrict__ std,

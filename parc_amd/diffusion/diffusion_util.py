@@ -1,6 +1,10 @@
 """Names the sampler and the loss share with the reference's trainer (reference diffusion/diffusion_util.py:6-17,65-69 and
-diffusion/mdm.py:39-55, :63-67): same members, same values."""
+diffusion/mdm.py:39-55, :63-67): same members, same values.  Below them, what the callers of the generator's device kernels share when
+they fill a configuration structure and its tables (include/parc_mdm_loss.h, parc_mdm_guide.h, parc_mdm_gen.h)."""
 import enum
+
+import numpy as np
+import torch
 
 
 class RelativeZStyle(enum.Enum):
@@ -91,3 +95,37 @@ class LossType(enum.Enum):
     SIMPLE_BODY_POS_LOSS = 13
     BODY_POS_CONSISTENCY_LOSS = 14
     VEL_FK_BODY_POS_LOSS = 15
+
+
+# ---------------------------------------------------------------------- tables of the device kernels
+def set_feature_layout(c, features):
+    """feat_dim and the five slice offsets of a parc_mdm_{loss,guide,gen}_cfg_t, from the MDMMotionLoss that registered the features; a
+    component the layout does not have is -1"""
+    c.feat_dim = features._motion_frame_dof
+    off = lambda name: features._feature_slices[features.MDMFrameType[name]].start if name in features._component_names else -1
+    c.off_root_pos, c.off_root_rot, c.off_joint_rot = off("ROOT_POS"), off("ROOT_ROT"), off("JOINT_ROT")
+    c.off_joint_pos, c.off_contacts = off("JOINT_POS"), off("CONTACTS")
+
+
+def set_local_grid(c, features):
+    """ox, oy, half_x, half_y of a parc_mdm_{loss,guide}_cfg_t: the reference's float32 arithmetic on the cell size"""
+    dx = np.float32(features._dx)
+    c.ox, c.oy = float(-dx * np.float32(features._num_x_neg)), float(-dx * np.float32(features._num_y_neg))
+    c.half_x = c.half_y = float(dx / np.float32(2.0))
+
+
+def local_grid_axes(features):
+    """(grid_x [X], grid_y [Y]) on the features' device: the host's linspace, copied"""
+    X, Y = features._grid_dim_x, features._grid_dim_y
+    return (torch.linspace(0.0, (X - 1.0) * features._dxdy[0].item(), X).to(features._device),
+            torch.linspace(0.0, (Y - 1.0) * features._dxdy[1].item(), Y).to(features._device))
+
+
+def pack_body_points(body_points, device):
+    """per-body list of [num points of body b, 3] -> (points [max(P, 1), 3], point_start [nb + 1] int32, P) on the device"""
+    counts = [int(p.shape[0]) for p in body_points]
+    start = torch.zeros(len(counts) + 1, dtype=torch.int32)
+    start[1:] = torch.cumsum(torch.tensor(counts), 0)
+    P = int(start[-1])
+    pts = torch.cat([p.detach().to(device="cpu", dtype=torch.float32).reshape(-1, 3) for p in body_points]) if P else torch.zeros((1, 3))
+    return pts.contiguous().to(device), start.to(device), P

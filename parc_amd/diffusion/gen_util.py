@@ -32,8 +32,8 @@ from ..util.motion_util import MotionFrames
 from . import diffusion_util
 from .mdm_guidance import guidance_params_from_settings
 from .mdm_loss import MDMMotionLoss
-
 _DEVICE_COMPONENTS = ("ROOT_POS", "ROOT_ROT", "JOINT_POS", "JOINT_ROT", "CONTACTS")
+
 # the attributes MotionGenDeepMimicEnv reads from its planner
 FIELDS = ("_num_prev_states", "_sequence_fps", "_dx", "_dy", "_num_x_neg", "_num_x_pos", "_num_y_neg", "_num_y_pos", "_target_type")
 
@@ -204,10 +204,8 @@ class MDMGenIO:
         from .. import _hip_mdm_gen as H
         F = self._features
         c = H.MdmGenCfgS()
-        c.num_frames, c.seq_len, c.num_prev_states, c.feat_dim = int(T), int(S), self._num_prev_states, F._motion_frame_dof
-        off = lambda name: F._feature_slices[self.MDMFrameType[name]].start if name in F._component_names else -1
-        c.off_root_pos, c.off_root_rot, c.off_joint_rot = off("ROOT_POS"), off("ROOT_ROT"), off("JOINT_ROT")
-        c.off_joint_pos, c.off_contacts = off("JOINT_POS"), off("CONTACTS")
+        diffusion_util.set_feature_layout(c, F)
+        c.num_frames, c.seq_len, c.num_prev_states = int(T), int(S), self._num_prev_states
         c.dim_x, c.dim_y = F._grid_dim_x, F._grid_dim_y
         c.z_style = H.Z_ROOT_FLOOR if self._relative_z_style == "RELATIVE_TO_ROOT_FLOOR" else H.Z_ROOT
         c.rot_type = {"DEFAULT": H.ROT_DEFAULT, "EXP_MAP": H.ROT_EXP_MAP, "QUAT": H.ROT_QUAT}[F._rot_type]

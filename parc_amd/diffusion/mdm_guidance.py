@@ -145,30 +145,20 @@ class MDMGuidance:
         key = id(body_points)
         hit = self._packed.get(key)
         if hit is None or hit[0] is not body_points:
-            counts = [int(p.shape[0]) for p in body_points]
-            assert len(counts) == self._char_model.get_num_joints()
-            start = torch.zeros(len(counts) + 1, dtype=torch.int32)
-            start[1:] = torch.cumsum(torch.tensor(counts), 0)
-            P = int(start[-1])
-            pts = torch.cat([p.detach().to(device="cpu", dtype=torch.float32).reshape(-1, 3) for p in body_points]) if P else torch.zeros((1, 3))
-            hit = (body_points, pts.contiguous().to(self._device), start.to(self._device), P)
+            assert len(body_points) == self._char_model.get_num_joints()
+            hit = (body_points,) + diffusion_util.pack_body_points(body_points, self._device)
             self._packed[key] = hit
         return hit[1:]
 
     def device_cfg(self, S, gp, enabled, P):
         """parc_mdm_guide_cfg_t of a call"""
-        import numpy as np
         from .. import _hip_mdm_guide as H
         F = self._features
         c = H.MdmGuideCfgS()
-        c.seq_len, c.feat_dim = int(S), F._motion_frame_dof
-        off = lambda name: F._feature_slices[self.MDMFrameType[name]].start if name in F._component_names else -1
-        c.off_root_pos, c.off_root_rot, c.off_joint_rot = off("ROOT_POS"), off("ROOT_ROT"), off("JOINT_ROT")
-        c.off_joint_pos, c.off_contacts = off("JOINT_POS"), off("CONTACTS")
+        diffusion_util.set_feature_layout(c, F)
+        diffusion_util.set_local_grid(c, F)
+        c.seq_len = int(S)
         c.dim_x, c.dim_y, c.enabled, c.num_points = F._grid_dim_x, F._grid_dim_y, enabled, int(P)
-        dx = np.float32(F._dx)
-        c.ox, c.oy = float(-dx * np.float32(F._num_x_neg)), float(-dx * np.float32(F._num_y_neg))
-        c.half_x = c.half_y = float(dx / np.float32(2.0))
         c.max_h, c.base_z = float(F._max_h), _BASE_Z
         c.guidance_str = float(gp.guidance_str)
         for t, v in enumerate(self._weights(gp)):
@@ -179,10 +169,7 @@ class MDMGuidance:
 
     def _grid_points(self):
         if self._grid is None:
-            F = self._features
-            X, Y = F._grid_dim_x, F._grid_dim_y
-            self._grid = (torch.linspace(0.0, (X - 1.0) * F._dxdy[0].item(), X).to(self._device),
-                          torch.linspace(0.0, (Y - 1.0) * F._dxdy[1].item(), Y).to(self._device))
+            self._grid = diffusion_util.local_grid_axes(self._features)
         return self._grid
 
     def _lds_bytes(self, c):

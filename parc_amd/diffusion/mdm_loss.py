@@ -296,27 +296,18 @@ class MDMMotionLoss:
             km, dev = self._char_model, self._device
             nb = km.get_num_joints()
             samples = self._char_point_samples if self._char_point_samples is not None else [torch.zeros((0, 3)) for _ in range(nb)]
-            start = np.zeros(nb + 1, dtype=np.int32)
-            start[1:] = np.cumsum([int(p.shape[0]) for p in samples])
-            points = torch.cat([p.to(torch.float32).cpu() for p in samples], dim=0) if start[-1] else torch.zeros((1, 3))
-            X, Y = self._grid_dim_x, self._grid_dim_y
-            dx = np.float32(self._dx)
+            points, start, P = diffusion_util.pack_body_points(samples, dev)
             c = H.MdmLossCfgS()
-            c.feat_dim, c.ref_idx = self._motion_frame_dof, self._num_prev_states - 1
-            off = lambda name: self._feature_slices[self.MDMFrameType[name]].start if name in self._component_names else -1
-            c.off_root_pos, c.off_root_rot, c.off_joint_rot = off("ROOT_POS"), off("ROOT_ROT"), off("JOINT_ROT")
-            c.off_joint_pos, c.off_contacts = off("JOINT_POS"), off("CONTACTS")
-            c.dim_x, c.dim_y, c.num_points = X, Y, int(start[-1])
-            c.ox, c.oy = float(-dx * np.float32(self._num_x_neg)), float(-dx * np.float32(self._num_y_neg))
-            c.half_x = c.half_y = float(dx / np.float32(2.0))
+            diffusion_util.set_feature_layout(c, self)
+            diffusion_util.set_local_grid(c, self)
+            c.ref_idx = self._num_prev_states - 1
+            c.dim_x, c.dim_y, c.num_points = self._grid_dim_x, self._grid_dim_y, P
             c.max_h, c.base_z = float(self._max_h), float(self._min_h - 5.0)
             c.dt, c.target_eps = 1.0 / self._sequence_fps, self._target_dir_len_eps
             for t, v in enumerate(self._w):
                 c.w[t] = v
-            self._device_tables = {
-                "cfg": c, "points": points.contiguous().to(dev), "start": torch.from_numpy(start).to(dev),
-                "grid_x": torch.linspace(0.0, (X - 1.0) * self._dxdy[0].item(), X).to(dev),
-                "grid_y": torch.linspace(0.0, (Y - 1.0) * self._dxdy[1].item(), Y).to(dev)}
+            grid_x, grid_y = diffusion_util.local_grid_axes(self)
+            self._device_tables = {"cfg": c, "points": points, "start": start, "grid_x": grid_x, "grid_y": grid_y}
         return self._device_tables
 
     def _enabled_terms(self, true_motion_data):

@@ -228,7 +228,7 @@ def test_sanitized_program_runs_the_cases(tmp_path, km, g35, hostlib):
 
 
 # ------------------------------------------------------------------------------------------------------------------- the library
-def test_exports_sizes_and_abi(hostlib):
+def test_exports_sizes_and_abi(hostlib, km, g35):
     from parc_amd import _hip, _hip_mdm_guide as H
     assert {"parc_mdm_guide_step", "parc_mdm_guide_lds_bytes", "parc_mdm_guide_abi"} <= set(_hip.EXPORTED)
     assert "parc_mdm_guide.hip" in _hip.SOURCES and "parc_mdm_guide.hip" in _hip.DIAG_SOURCES
@@ -240,6 +240,17 @@ def test_exports_sizes_and_abi(hostlib):
     sizes = (ctypes.c_int * 2)()
     assert gh.host_lib(hostlib).mdm_guide_struct_sizes(sizes) == 2
     assert (sizes[0], sizes[1]) == (ctypes.sizeof(H.MdmGuideCfgS), ctypes.sizeof(_hip.CharModelS))
+    # the LDS of a workgroup, from the host build of the core: the formula of include/parc_mdm_guide.h for every case of the fixture, and
+    # the figure that header gives for the shipped configuration (S 16, 15 bodies, 31 x 31 grid, 304 points, D 91)
+    z, meta = g35
+    for case in meta["cases"]:
+        a = gh.Args(km, case, z)
+        c = a.cfg
+        assert gh.host_lib(hostlib).mdm_guide_lds_bytes_host(a.model, c) == \
+            H.lds_formula(c.seq_len, km.get_num_joints(), c.feat_dim, c.dim_x * c.dim_y, c.num_points), case["name"]
+    c = gh.Args(km, case_of(meta, "shipped"), z).cfg
+    assert (c.seq_len, km.get_num_joints(), c.dim_x, c.dim_y, c.num_points, c.feat_dim) == (16, 15, 31, 31, 304, 91)
+    assert gh.host_lib(hostlib).mdm_guide_lds_bytes_host(km.c_struct(), c) == 59780
 
 
 def test_argument_refusals_need_no_gpu(km, g35):
