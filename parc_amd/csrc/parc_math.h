@@ -1,25 +1,14 @@
 // Device quaternion / rotation math for the tracker kernels (gfx950).
 // Quaternions are xyzw, fp32, as in the reference's util/torch_util.py; each helper follows the
 // reference's operation order so results agree with it to a few ulp.
+// Here: the fast approximations (single-instruction primitives, polynomial sin / cos / atan2 / acos, the FMA-grouped product) and what
+// is built on them.  The types, the plain-fp32 algebra and the torch-exact maps are parc_rot.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "parc_rot.h"      // v3, q4, their operators, ld/st, the plain-fp32 torch-order functions and the torch-exact maps
+
 #define PARC_DEV __device__ __forceinline__
-
-struct q4 {
-    float x, y, z, w;
-};
-struct v3 {
-    float x, y, z;
-};
-
-PARC_DEV v3 mk3(float x, float y, float z) { return v3{x, y, z}; }
-PARC_DEV q4 mk4(float x, float y, float z, float w) { return q4{x, y, z, w}; }
-PARC_DEV v3 operator+(v3 a, v3 b) { return v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-PARC_DEV v3 operator-(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-PARC_DEV v3 operator*(float s, v3 a) { return v3{s * a.x, s * a.y, s * a.z}; }
-PARC_DEV float dot3(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-PARC_DEV v3 cross3(v3 a, v3 b) { return v3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
 // ---- single-instruction / short-polynomial primitives (each within ~1-2 ulp of the correctly rounded value; the
 // library versions cost 10-200 instructions per call and the post-step kernel is VALU-issue bound) -----------------
@@ -90,15 +79,9 @@ PARC_DEV q4 quat_mul(q4 a, q4 b) {
     return o;
 }
 
-// util/torch_util.py:60-66
-PARC_DEV v3 quat_rotate(q4 q, v3 v) {
-    v3 qv = mk3(q.x, q.y, q.z);
-    v3 t = 2.f * cross3(qv, v);
-    v3 c = cross3(qv, t);
-    return v3{v.x + q.w * t.x + c.x, v.y + q.w * t.y + c.y, v.z + q.w * t.z + c.z};
-}
-
-PARC_DEV q4 quat_conj(q4 q) { return q4{-q.x, -q.y, -q.z, q.w}; }
+// the long names of the plain-fp32 rotation and conjugate (parc_rot.h), which the tracker kernels use throughout
+PARC_DEV v3 quat_rotate(q4 q, v3 v) { return qrot(q, v); }
+PARC_DEV q4 quat_conj(q4 q) { return qconj(q); }
 
 // util/torch_util.py:33-38
 PARC_DEV q4 quat_pos(q4 q) {
@@ -148,31 +131,9 @@ PARC_DEV q4 exp_map_to_quat(v3 em) {
     return axis_angle_to_quat(ax, a);
 }
 
-// Library-precision variants for the one-time clip database build: the stored frame quaternions then equal the
-// reference's to the last bit, which matters because slerp between nearly identical frames amplifies input ulps.
-PARC_DEV q4 quat_unit_lib(q4 q) {
-#pragma clang fp contract(off)      // op by op like torch: no fused multiply-adds in the *_lib functions
-    float n = fmaxf(sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w), 1e-9f);
-    return q4{q.x / n, q.y / n, q.z / n, q.w / n};
-}
-PARC_DEV q4 axis_angle_to_quat_lib(v3 axis, float angle) {
-#pragma clang fp contract(off)
-    float theta = angle / 2.f;
-    float n = fmaxf(sqrtf((axis.x * axis.x + axis.y * axis.y) + axis.z * axis.z), 1e-9f);
-    float s = sinf(theta);
-    return quat_unit_lib(q4{axis.x / n * s, axis.y / n * s, axis.z / n * s, cosf(theta)});
-}
-PARC_DEV q4 exp_map_to_quat_lib(v3 em) {
-#pragma clang fp contract(off)
-    float a = sqrtf((em.x * em.x + em.y * em.y) + em.z * em.z);
-    v3 ax = v3{em.x / a, em.y / a, em.z / a};
-    a = atan2f(sinf(a), cosf(a));
-    if (!(fabsf(a) > 1e-5f)) {
-        ax = mk3(0.f, 0.f, 1.f);
-        a = 0.f;
-    }
-    return axis_angle_to_quat_lib(ax, a);
-}
+// The library-precision variants for the one-time clip database build are the torch-exact maps of parc_rot.h (qunit, aa_to_quat,
+// em_to_quat): the stored frame quaternions then equal the reference's to the last bit, which matters because slerp between nearly
+// identical frames amplifies input ulps.
 
 // util/torch_util.py:68-88
 PARC_DEV void quat_to_axis_angle(q4 qin, v3 &axis, float &angle) {
@@ -285,8 +246,3 @@ PARC_DEV void quat_to_tan_norm(q4 q, float *o) {
     o[4] = q.w * uy + q.z * ux;
     o[5] = 1.f + (q.x * uy - q.y * ux);
 }
-
-PARC_DEV q4 ld4(const float *p) { return q4{p[0], p[1], p[2], p[3]}; }
-PARC_DEV v3 ld3(const float *p) { return v3{p[0], p[1], p[2]}; }
-PARC_DEV void st4(float *p, q4 q) { p[0] = q.x; p[1] = q.y; p[2] = q.z; p[3] = q.w; }
-PARC_DEV void st3(float *p, v3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/parc_mdm_batch.h"
+#include "parc_rot.h"       // v3, q4, qmul (:577-594 quat_multiply, the grouping the canonicalisation uses), qrot (:61-66)
 
 #if defined(__HIPCC__)
 #define PARC_MDM_FN __device__ __forceinline__
@@ -36,26 +37,19 @@
 
 namespace parc_mdm {
 
-struct Q {
-    float x, y, z, w;
-};
-struct V {
-    float x, y, z;
-};
-
 PARC_MDM_FN float quiet_nan() { return __builtin_nanf(""); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // util/torch_util.py
 // ---------------------------------------------------------------------------------------------------------------------------------
 // :41-58 quat_mul (the grouping the FK uses)
-PARC_MDM_FN Q quat_mul(Q a, Q b) {
+PARC_MDM_FN q4 quat_mul(q4 a, q4 b) {
     const float ww = (a.z + a.x) * (b.x + b.y);
     const float yy = (a.w - a.y) * (b.w + b.z);
     const float zz = (a.w + a.y) * (b.w - b.z);
     const float xx = (ww + yy) + zz;
     const float qq = 0.5f * (xx + (a.z - a.x) * (b.x - b.y));
-    Q o;
+    q4 o;
     o.w = (qq - ww) + (a.z - a.y) * (b.y - b.z);
     o.x = (qq - xx) + (a.x + a.w) * (b.x + b.w);
     o.y = (qq - yy) + (a.w - a.x) * (b.y + b.z);
@@ -63,50 +57,31 @@ PARC_MDM_FN Q quat_mul(Q a, Q b) {
     return o;
 }
 
-// :577-594 quat_multiply (the grouping the canonicalisation uses)
-PARC_MDM_FN Q quat_multiply(Q a, Q b) {
-    Q o;
-    o.x = ((a.w * b.x + a.x * b.w) + a.y * b.z) - a.z * b.y;
-    o.y = ((a.w * b.y - a.x * b.z) + a.y * b.w) + a.z * b.x;
-    o.z = ((a.w * b.z + a.x * b.y) - a.y * b.x) + a.z * b.w;
-    o.w = ((a.w * b.w - a.x * b.x) - a.y * b.y) - a.z * b.z;
-    return o;
-}
-
-// :61-66
-PARC_MDM_FN V quat_rotate(Q q, V v) {
-    const float tx = 2.f * (q.y * v.z - q.z * v.y), ty = 2.f * (q.z * v.x - q.x * v.z), tz = 2.f * (q.x * v.y - q.y * v.x);
-    V o;
-    o.x = (v.x + q.w * tx) + (q.y * tz - q.z * ty);
-    o.y = (v.y + q.w * ty) + (q.z * tx - q.x * tz);
-    o.z = (v.z + q.w * tz) + (q.x * ty - q.y * tx);
-    return o;
-}
-
 // :471-479
-PARC_MDM_FN float calc_heading(Q q) {
-    const V d = quat_rotate(q, V{1.f, 0.f, 0.f});
+PARC_MDM_FN float calc_heading(q4 q) {
+    const v3 d = qrot(q, v3{1.f, 0.f, 0.f});
     return atan2f(d.y, d.x);
 }
 
-// :312-317 about +z, :492-499 with the angle negated by the caller
-PARC_MDM_FN Q heading_quat(float angle) {
+// :312-317 about +z, :492-499 with the angle negated by the caller.  Not aa_to_quat (parc_rot.h) about +z: its x and y are
+// 0 / n * sin, -0 for a negative angle, where this function gives +0, and a zero's sign is a bit of the result
+PARC_MDM_FN q4 heading_quat(float angle) {
     const float theta = angle / 2.f;
     const float z = 1.f * sinf(theta), w = cosf(theta);
     const float n = fmaxf(sqrtf(((0.f + 0.f) + z * z) + w * w), 1e-9f);
-    return Q{0.f / n, 0.f / n, z / n, w / n};
+    return q4{0.f / n, 0.f / n, z / n, w / n};
 }
 
 // :444-468
-PARC_MDM_FN Q slerp(Q q0, Q q1, float t) {
+PARC_MDM_FN q4 slerp(q4 q0, q4 q1, float t) {
     float c = ((q0.x * q1.x + q0.y * q1.y) + q0.z * q1.z) + q0.w * q1.w;
-    if (c < 0.f) q1 = Q{-q1.x, -q1.y, -q1.z, -q1.w};
+    if (c < 0.f) q1 = q4{-q1.x, -q1.y, -q1.z, -q1.w};
     c = fabsf(c);
     const float ht = acosf(c);
     const float s = sqrtf(1.0f - c * c);
     const float ra = sinf((1.f - t) * ht) / s, rb = sinf(t * ht) / s;
-    Q o = Q{ra * q0.x + rb * q1.x, ra * q0.y + rb * q1.y, ra * q0.z + rb * q1.z, ra * q0.w + rb * q1.w};
-    if (fabsf(s) < 0.001f) o = Q{0.5f * q0.x + 0.5f * q1.x, 0.5f * q0.y + 0.5f * q1.y, 0.5f * q0.z + 0.5f * q1.z, 0.5f * q0.w + 0.5f * q1.w};
+    q4 o = q4{ra * q0.x + rb * q1.x, ra * q0.y + rb * q1.y, ra * q0.z + rb * q1.z, ra * q0.w + rb * q1.w};
+    if (fabsf(s) < 0.001f) o = q4{0.5f * q0.x + 0.5f * q1.x, 0.5f * q0.y + 0.5f * q1.y, 0.5f * q0.z + 0.5f * q1.z, 0.5f * q0.w + 0.5f * q1.w};
     if (c >= 1.f) o = q0;
     return o;
 }
@@ -143,14 +118,14 @@ PARC_MDM_FN Query make_query(const parc_motion_lib_t &ml, int64_t id, float time
 
 PARC_MDM_FN float lerp(float a, float b, float t) { return (1.0f - t) * a + t * b; }
 
-PARC_MDM_FN Q query_quat(const Query &fq, int b) {
+PARC_MDM_FN q4 query_quat(const Query &fq, int b) {
     const float *a = fq.row0 + 4 * b, *c = fq.row1 + 4 * b;
-    return slerp(Q{a[0], a[1], a[2], a[3]}, Q{c[0], c[1], c[2], c[3]}, fq.blend);
+    return slerp(q4{a[0], a[1], a[2], a[3]}, q4{c[0], c[1], c[2], c[3]}, fq.blend);
 }
 
-PARC_MDM_FN V query_root_pos(const parc_motion_lib_t &ml, const Query &fq, int64_t id) {
+PARC_MDM_FN v3 query_root_pos(const parc_motion_lib_t &ml, const Query &fq, int64_t id) {
     const float *p0 = fq.row0 + ml.off_pos, *p1 = fq.row1 + ml.off_pos;
-    V p = V{lerp(p0[0], p1[0], fq.blend), lerp(p0[1], p1[1], fq.blend), lerp(p0[2], p1[2], fq.blend)};
+    v3 p = v3{lerp(p0[0], p1[0], fq.blend), lerp(p0[1], p1[1], fq.blend), lerp(p0[2], p1[2], fq.blend)};
     if (fq.wrap) {
         const float *d = ml.pos_delta + 3 * id;
         p.x = p.x + fq.loop_phase * d[0], p.y = p.y + fq.loop_phase * d[1], p.z = p.z + fq.loop_phase * d[2];
@@ -190,14 +165,14 @@ PARC_MDM_FN void window_lane(const parc_char_model_t &m, const parc_motion_lib_t
     const float start = start_times[s];
     // the reference frame, looked up again by every lane of the sample
     const Query rq = make_query(ml, id, start + motion_times[cfg.ref_idx]);
-    const V cpos = query_root_pos(ml, rq, id);
-    const Q hinv = heading_quat(-calc_heading(query_quat(rq, 0)));
+    const v3 cpos = query_root_pos(ml, rq, id);
+    const q4 hinv = heading_quat(-calc_heading(query_quat(rq, 0)));
 
     const Query fq = make_query(ml, id, start + motion_times[k]);
-    V p = query_root_pos(ml, fq, id);
+    v3 p = query_root_pos(ml, fq, id);
     if (center_h) p.z = p.z - center_h[s];
-    p = quat_rotate(hinv, V{p.x - cpos.x, p.y - cpos.y, p.z - cpos.z});
-    const Q r = quat_multiply(hinv, query_quat(fq, 0));
+    p = qrot(hinv, v3{p.x - cpos.x, p.y - cpos.y, p.z - cpos.z});
+    const q4 r = qmul(hinv, query_quat(fq, 0));
     root_pos[row * 3 + 0] = p.x, root_pos[row * 3 + 1] = p.y, root_pos[row * 3 + 2] = p.z;
     root_rot[row * 4 + 0] = r.x, root_rot[row * 4 + 1] = r.y, root_rot[row * 4 + 2] = r.z, root_rot[row * 4 + 3] = r.w;
     {
@@ -208,17 +183,17 @@ PARC_MDM_FN void window_lane(const parc_char_model_t &m, const parc_motion_lib_t
     PARC_MDM_WS(0, 0) = p.x, PARC_MDM_WS(0, 1) = p.y, PARC_MDM_WS(0, 2) = p.z;
     PARC_MDM_WS(0, 3) = r.x, PARC_MDM_WS(0, 4) = r.y, PARC_MDM_WS(0, 5) = r.z, PARC_MDM_WS(0, 6) = r.w;
     for (int j = 1; j < B; ++j) {
-        const Q jq = query_quat(fq, j);
+        const q4 jq = query_quat(fq, j);
         float *jr = joint_rot + (row * (B - 1) + (j - 1)) * 4;
         jr[0] = jq.x, jr[1] = jq.y, jr[2] = jq.z, jr[3] = jq.w;
         int par = m.parent[j];
         if (par < 0 || par >= j) par = 0;
-        const V pp = V{PARC_MDM_WS(par, 0), PARC_MDM_WS(par, 1), PARC_MDM_WS(par, 2)};
-        const Q pr = Q{PARC_MDM_WS(par, 3), PARC_MDM_WS(par, 4), PARC_MDM_WS(par, 5), PARC_MDM_WS(par, 6)};
-        const V wt = quat_rotate(pr, V{m.local_translation[j][0], m.local_translation[j][1], m.local_translation[j][2]});
-        const V cp = V{pp.x + wt.x, pp.y + wt.y, pp.z + wt.z};
-        const Q lr = Q{m.local_rotation[j][0], m.local_rotation[j][1], m.local_rotation[j][2], m.local_rotation[j][3]};
-        const Q cr = quat_mul(pr, quat_mul(lr, jq));
+        const v3 pp = v3{PARC_MDM_WS(par, 0), PARC_MDM_WS(par, 1), PARC_MDM_WS(par, 2)};
+        const q4 pr = q4{PARC_MDM_WS(par, 3), PARC_MDM_WS(par, 4), PARC_MDM_WS(par, 5), PARC_MDM_WS(par, 6)};
+        const v3 wt = qrot(pr, v3{m.local_translation[j][0], m.local_translation[j][1], m.local_translation[j][2]});
+        const v3 cp = v3{pp.x + wt.x, pp.y + wt.y, pp.z + wt.z};
+        const q4 lr = q4{m.local_rotation[j][0], m.local_rotation[j][1], m.local_rotation[j][2], m.local_rotation[j][3]};
+        const q4 cr = quat_mul(pr, quat_mul(lr, jq));
         PARC_MDM_WS(j, 0) = cp.x, PARC_MDM_WS(j, 1) = cp.y, PARC_MDM_WS(j, 2) = cp.z;
         PARC_MDM_WS(j, 3) = cr.x, PARC_MDM_WS(j, 4) = cr.y, PARC_MDM_WS(j, 5) = cr.z, PARC_MDM_WS(j, 6) = cr.w;
         float *bp = body_pos + (row * (B - 1) + (j - 1)) * 3;
@@ -227,10 +202,10 @@ PARC_MDM_FN void window_lane(const parc_char_model_t &m, const parc_motion_lib_t
 #undef PARC_MDM_WS
     if (k == 0 && future_pos) {
         const Query tq = make_query(ml, id, future_time[s]);
-        V f = query_root_pos(ml, tq, id);
+        v3 f = query_root_pos(ml, tq, id);
         f.x = f.x + future_noise[(size_t)s * 3 + 0], f.y = f.y + future_noise[(size_t)s * 3 + 1], f.z = f.z + future_noise[(size_t)s * 3 + 2];
-        f = quat_rotate(hinv, V{f.x - cpos.x, f.y - cpos.y, f.z - cpos.z});
-        const Q fr = quat_multiply(hinv, query_quat(tq, 0));
+        f = qrot(hinv, v3{f.x - cpos.x, f.y - cpos.y, f.z - cpos.z});
+        const q4 fr = qmul(hinv, query_quat(tq, 0));
         future_pos[(size_t)s * 3 + 0] = f.x, future_pos[(size_t)s * 3 + 1] = f.y, future_pos[(size_t)s * 3 + 2] = f.z;
         future_rot[(size_t)s * 4 + 0] = fr.x, future_rot[(size_t)s * 4 + 1] = fr.y, future_rot[(size_t)s * 4 + 2] = fr.z;
         future_rot[(size_t)s * 4 + 3] = fr.w;
@@ -331,7 +306,7 @@ PARC_MDM_FN void hf_sample(const parc_motion_lib_t &ml, const parc_mdm_cfg_t &cf
 
     // 2. gather: generic grid point turned by the reference heading + reference root xy -> terrain cell -> height and band
     const Query rq = make_query(ml, id, start + motion_times[cfg.ref_idx]);
-    const V cpos = query_root_pos(ml, rq, id);
+    const v3 cpos = query_root_pos(ml, rq, id);
     const float heading = calc_heading(query_quat(rq, 0));
     const float ch = cosf(heading), sh = sinf(heading);
     for (int k = lane; k < XY; k += lanes) {

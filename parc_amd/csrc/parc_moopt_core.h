@@ -13,21 +13,12 @@
 #include "../../include/parc_moopt.h"
 #include "parc_sdf_core.h"
 
+#include "parc_rot.h"       // v3, ld3, st3, mk3, dot3
+
 #if defined(__HIPCC__)
-#include "parc_math.h"      // v3, ld3, st3, mk3, dot3
+#define PARC_MO_FN __device__ __forceinline__
 #else
-// the host's stand-ins for the few parc_math.h names the bodies below use
-#define PARC_DEV static inline
-struct v3 {
-    float x, y, z;
-};
-PARC_DEV v3 mk3(float x, float y, float z) { return v3{x, y, z}; }
-PARC_DEV v3 operator+(v3 a, v3 b) { return v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-PARC_DEV v3 operator-(v3 a, v3 b) { return v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-PARC_DEV v3 operator*(float s, v3 a) { return v3{s * a.x, s * a.y, s * a.z}; }
-PARC_DEV float dot3(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-PARC_DEV v3 ld3(const float *p) { return v3{p[0], p[1], p[2]}; }
-PARC_DEV void st3(float *p, v3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+#define PARC_MO_FN static inline
 #endif
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -39,17 +30,17 @@ PARC_DEV void st3(float *p, v3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct tt_args { float c, c2, jerk_limit; };
 
-PARC_DEV v3 tt_vel_err(const float *__restrict__ pos, const float *__restrict__ src_vel, int B, int t, int b) {
+PARC_MO_FN v3 tt_vel_err(const float *__restrict__ pos, const float *__restrict__ src_vel, int B, int t, int b) {
     return (ld3(pos + ((size_t)(t + 1) * B + b) * 3) - ld3(pos + ((size_t)t * B + b) * 3)) - ld3(src_vel + ((size_t)t * B + b) * 3);
 }
-PARC_DEV v3 tt_third_diff(const float *__restrict__ pos, int B, int t, int b) {
+PARC_MO_FN v3 tt_third_diff(const float *__restrict__ pos, int B, int t, int b) {
     const v3 p0 = ld3(pos + ((size_t)t * B + b) * 3), p1 = ld3(pos + ((size_t)(t + 1) * B + b) * 3), p2 = ld3(pos + ((size_t)(t + 2) * B + b) * 3),
              p3 = ld3(pos + ((size_t)(t + 3) * B + b) * 3);
     return ((p3 - p2) - (p2 - p1)) - ((p2 - p1) - (p1 - p0));      // (a[t+1] - a[t]) of the velocities' differences, like the torch expression
 }
 
 // the three partial terms of (t, b) of ONE motion of T frames; every pointer is the motion's first row, i = t * B + b
-PARC_DEV void tt_forward_body(int T, int B, int t, int b, int i, const float *__restrict__ pos, const float *__restrict__ rot_err_sq,
+PARC_MO_FN void tt_forward_body(int T, int B, int t, int b, int i, const float *__restrict__ pos, const float *__restrict__ rot_err_sq,
                               const float *__restrict__ src_vel, const float *__restrict__ keep, const float *__restrict__ pair_contact, tt_args a,
                               float &sm, float &sl, float &jl) {
     sm = 0.f, sl = 0.f, jl = 0.f;
@@ -67,7 +58,7 @@ PARC_DEV void tt_forward_body(int T, int B, int t, int b, int i, const float *__
 
 // adjoint at (t, b) of ONE motion of T frames for the cotangents (w0, w1, w2) of its three sums: returns the gradient of p[t, b];
 // g_r is written for t < T - 1 only (has_r tells)
-PARC_DEV v3 tt_backward_body(int T, int B, int t, int b, int i, const float *__restrict__ pos, const float *__restrict__ rot_err_sq,
+PARC_MO_FN v3 tt_backward_body(int T, int B, int t, int b, int i, const float *__restrict__ pos, const float *__restrict__ rot_err_sq,
                              const float *__restrict__ src_vel, const float *__restrict__ keep, const float *__restrict__ pair_contact, tt_args a,
                              float w0, float w1, float w2, float &g_r, bool &has_r) {
     v3 g = mk3(0.f, 0.f, 0.f);
@@ -97,7 +88,7 @@ PARC_DEV v3 tt_backward_body(int T, int B, int t, int b, int i, const float *__r
 
 // The motion of packed frame f: its id m, first frame s and length T, checked against the tables (a frame the tables do not cover
 // reads nothing).
-PARC_DEV bool tt_seg_of(int f, int N, int M, const int32_t *__restrict__ seg_start, const int32_t *__restrict__ seg_of_frame, int &m, int &s,
+PARC_MO_FN bool tt_seg_of(int f, int N, int M, const int32_t *__restrict__ seg_start, const int32_t *__restrict__ seg_of_frame, int &m, int &s,
                         int &T) {
     m = seg_of_frame[f];
     if (m < 0 || m >= M) return false;
@@ -108,7 +99,7 @@ PARC_DEV bool tt_seg_of(int f, int N, int M, const int32_t *__restrict__ seg_sta
 }
 
 // thread i of parc_temporal_terms_seg: (frame, body) i of the packed [N, B] grid
-PARC_DEV void tt_seg_thread(int i, int N, int B, int M, const int32_t *__restrict__ seg_start, const int32_t *__restrict__ seg_of_frame,
+PARC_MO_FN void tt_seg_thread(int i, int N, int B, int M, const int32_t *__restrict__ seg_start, const int32_t *__restrict__ seg_of_frame,
                             const float *__restrict__ pos, const float *__restrict__ rot_err_sq, const float *__restrict__ src_vel,
                             const float *__restrict__ keep, const float *__restrict__ pair_contact, tt_args a, float *partial) {
     const int f = i / B, b = i - f * B;
@@ -126,7 +117,7 @@ PARC_DEV void tt_seg_thread(int i, int N, int B, int M, const int32_t *__restric
 }
 
 // thread i of parc_temporal_terms_seg_grad; w [3, M]: cotangents of the three sums of every motion
-PARC_DEV void tt_seg_grad_thread(int i, int N, int B, int M, const int32_t *__restrict__ seg_start, const int32_t *__restrict__ seg_of_frame,
+PARC_MO_FN void tt_seg_grad_thread(int i, int N, int B, int M, const int32_t *__restrict__ seg_start, const int32_t *__restrict__ seg_of_frame,
                                  const float *__restrict__ pos, const float *__restrict__ rot_err_sq, const float *__restrict__ src_vel,
                                  const float *__restrict__ keep, const float *__restrict__ pair_contact, tt_args a, const float *__restrict__ w,
                                  float *g_pos, float *g_rot_err_sq) {
@@ -151,7 +142,7 @@ PARC_DEV void tt_seg_grad_thread(int i, int N, int B, int M, const int32_t *__re
 // Terrain query with a terrain per row
 // ---------------------------------------------------------------------------------------------------------------------------------
 // point idx of the flat [n_rows * points_per_row] grid: value and arg-min column by the rules of points_hf_sdf_kernel
-PARC_DEV void ragged_thread(size_t idx, int points_per_row, const float *__restrict__ points, const int32_t *__restrict__ row_terrain,
+PARC_MO_FN void ragged_thread(size_t idx, int points_per_row, const float *__restrict__ points, const int32_t *__restrict__ row_terrain,
                             int n_terrains, const parc_moopt_terrain_t *__restrict__ table, const float *__restrict__ pool, int inverted,
                             float radius, float *__restrict__ out, int32_t *__restrict__ out_cell) {
     const size_t row = idx / (size_t)points_per_row;
@@ -174,7 +165,7 @@ PARC_DEV void ragged_thread(size_t idx, int points_per_row, const float *__restr
 
 // Adjoint at point idx: the piecewise expression of points_hf_sdf_grad_kernel (abs -> sign, clamp(min=0) + norm -> unit vector of the
 // positive part, max -> its first arg-max, clamp(max=0) -> passes at <= 0) for the column the forward pass selected.
-PARC_DEV void ragged_grad_thread(size_t idx, int points_per_row, const float *__restrict__ points, const int32_t *__restrict__ row_terrain,
+PARC_MO_FN void ragged_grad_thread(size_t idx, int points_per_row, const float *__restrict__ points, const int32_t *__restrict__ row_terrain,
                                  int n_terrains, const parc_moopt_terrain_t *__restrict__ table, const float *__restrict__ pool, int inverted,
                                  const int32_t *__restrict__ cell, const float *__restrict__ g_out, float *__restrict__ g_points) {
     const size_t row = idx / (size_t)points_per_row;
@@ -222,7 +213,7 @@ PARC_DEV void ragged_grad_thread(size_t idx, int points_per_row, const float *__
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The block of plane `plane` that motion m owns: elements [e0, e1) of values; false (an empty block) when the segment is empty or does
 // not lie inside [0, n_rows].
-PARC_DEV bool segsum_block(int plane, int m, int n_rows, int width, const int32_t *__restrict__ seg_start, size_t &e0, size_t &e1) {
+PARC_MO_FN bool segsum_block(int plane, int m, int n_rows, int width, const int32_t *__restrict__ seg_start, size_t &e0, size_t &e1) {
     const int s = seg_start[m], e = seg_start[m + 1];
     if (s < 0 || e > n_rows || e <= s) return false;
     e0 = ((size_t)plane * n_rows + s) * width;
@@ -231,7 +222,7 @@ PARC_DEV bool segsum_block(int plane, int m, int n_rows, int width, const int32_
 }
 
 // partial sum `lane` of the block: elements e0 + lane, e0 + lane + 256, ... in ascending order
-PARC_DEV float segsum_lane(const float *__restrict__ values, size_t e0, size_t e1, int lane) {
+PARC_MO_FN float segsum_lane(const float *__restrict__ values, size_t e0, size_t e1, int lane) {
     float acc = 0.f;
     for (size_t e = e0 + lane; e < e1; e += PARC_MOOPT_SUM_LANES) acc += values[e];
     return acc;

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void motion_rows_kernel(parc_char_model_t m, p
     float *row = rows + (size_t)f * ml.row_stride;
     q4 q;
     if (b == 0) {
-        q = exp_map_to_quat_lib(mk3(fr[3], fr[4], fr[5]));        // motion_lib.py:418
+        q = em_to_quat(mk3(fr[3], fr[4], fr[5]));        // motion_lib.py:418
         st3(row + ml.off_pos, ld3(fr));
     } else {
         q = quat_pos(joint_dof_to_rot<true>(m, b, fr + 6, 1));     // motion_lib.py:420-421

@@ -15,11 +15,11 @@ PARC_DEV q4 joint_dof_to_rot(const parc_char_model_t &m, int b, const float *dof
     if (jt == PARC_JOINT_HINGE) {
         v3 ax = mk3(m.joint_axis[b][0], m.joint_axis[b][1], m.joint_axis[b][2]);
         float an = dof[m.dof_idx[b] * stride];
-        return LIB ? axis_angle_to_quat_lib(ax, an) : axis_angle_to_quat(ax, an);
+        return LIB ? aa_to_quat(ax, an) : axis_angle_to_quat(ax, an);
     } else if (jt == PARC_JOINT_SPHERICAL) {
         int d = m.dof_idx[b];
         v3 em = mk3(dof[d * stride], dof[(d + 1) * stride], dof[(d + 2) * stride]);
-        return LIB ? exp_map_to_quat_lib(em) : exp_map_to_quat(em);
+        return LIB ? em_to_quat(em) : exp_map_to_quat(em);
     }
     return mk4(0.f, 0.f, 0.f, 1.f);
 }

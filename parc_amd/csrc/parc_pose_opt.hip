@@ -15,56 +15,9 @@
 // rotations, body positions / rotations, and the vector-Jacobian product back.  This is what stage 2's motion optimiser
 // differentiates thousands of times per clip (tools/motion_opt/motion_optimization.py:203-213: exp_map_to_quat, KinCharModel.dof_to_rot,
 // forward_kinematics and their autograd); as torch ops it is ~190 autograd nodes per evaluation, here two launches.
-// Forward uses the library-precision maps (the values torch computes); the adjoint is exact for those formulas:
-//   q = a (x) b  bilinear          =>  g_a = g (x) conj(b),  g_b = conj(a) (x) g
-//   r = v + w t + u x t, t = 2 u x v  =>  g_w = g.t,  g_t = w g + g x u,  g_u = t x g + 2 v x g_t
-//   q = unit(n(axis) sin h, cos h), h = angle / 2   (torch_util.axis_angle_to_quat: both normalisations are projections at unit length)
+// Forward uses the torch-exact maps (the values torch computes); the adjoint is exact for those formulas.  Maps and adjoints are those of
+// parc_rot.h, so the same lines run on the host under the generator cores' CPU tests.
 // =============================================================================================
-struct aa_grad { v3 g_axis; float g_angle; };
-
-PARC_DEV aa_grad axis_angle_to_quat_bwd(v3 axis, float angle, q4 q, q4 g) {
-    // through quat_unit: q = raw / |raw| with |raw| = 1 up to rounding -> g_raw = g - (g.q) q
-    const float gq = g.x * q.x + g.y * q.y + g.z * q.z + g.w * q.w;
-    const q4 gr = q4{g.x - gq * q.x, g.y - gq * q.y, g.z - gq * q.z, g.w - gq * q.w};
-    const float h = 0.5f * angle;
-    const float sh = sinf(h), ch = cosf(h);
-    const float na = fmaxf(sqrtf(dot3(axis, axis)), 1e-9f);
-    const v3 a = mk3(axis.x / na, axis.y / na, axis.z / na);
-    const v3 grv = mk3(gr.x, gr.y, gr.z);
-    aa_grad o;
-    o.g_angle = 0.5f * (ch * dot3(a, grv) - sh * gr.w);
-    // through normalize(axis): g_axis = (I - a a^T) (sin h g_v) / |axis|
-    const v3 ga = mk3(sh * grv.x, sh * grv.y, sh * grv.z);
-    const float gaa = dot3(ga, a);
-    o.g_axis = mk3((ga.x - gaa * a.x) / na, (ga.y - gaa * a.y) / na, (ga.z - gaa * a.z) / na);
-    return o;
-}
-
-// torch_util.exp_map_to_quat = axis_angle_to_quat(e / |e|, wrap(|e|)), z axis / angle 0 below 1e-5 (that branch is constant)
-PARC_DEV v3 exp_map_to_quat_bwd(v3 em, q4 q, q4 g) {
-    const float raw = sqrtf((em.x * em.x + em.y * em.y) + em.z * em.z);
-    const float ang = atan2f(sinf(raw), cosf(raw));
-    if (!(fabsf(ang) > 1e-5f)) return mk3(0.f, 0.f, 0.f);
-    const v3 a = mk3(em.x / raw, em.y / raw, em.z / raw);
-    const aa_grad ag = axis_angle_to_quat_bwd(a, ang, q, g);
-    // axis = e / raw: J^T g = (g - (g.a) a) / raw;  angle = wrap(raw): d/de = a
-    const float ga = dot3(ag.g_axis, a);
-    return mk3((ag.g_axis.x - ga * a.x) / raw + ag.g_angle * a.x, (ag.g_axis.y - ga * a.y) / raw + ag.g_angle * a.y,
-               (ag.g_axis.z - ga * a.z) / raw + ag.g_angle * a.z);
-}
-
-PARC_DEV q4 qadd(q4 a, q4 b) { return q4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
-
-// cotangent of q for r = quat_rotate(q, v) = v + w t + u x t, t = 2 u x v (u = q.xyz), given the cotangent g of r
-PARC_DEV q4 quat_rotate_bwd_q(q4 q, v3 v, v3 g) {
-    const v3 u = mk3(q.x, q.y, q.z);
-    const v3 t = 2.f * cross3(u, v);
-    const v3 gxu = cross3(g, u);
-    const v3 gt = mk3(q.w * g.x + gxu.x, q.w * g.y + gxu.y, q.w * g.z + gxu.z);
-    const v3 gu = cross3(t, g) + 2.f * cross3(v, gt);
-    return q4{gu.x, gu.y, gu.z, dot3(g, t)};
-}
-
 __global__ __launch_bounds__(64) void pose_chain_fwd_kernel(parc_char_model_t m, int n, const float *__restrict__ root_pos,
                                                             const float *__restrict__ root_exp, const float *__restrict__ dof,
                                                             float *root_quat, float *joint_rot, float *body_pos, float *body_rot) {
@@ -73,7 +26,7 @@ __global__ __launch_bounds__(64) void pose_chain_fwd_kernel(parc_char_model_t m,
     const int B = m.num_bodies;
     q4 rot[PARC_MAX_BODIES];
     v3 pos[PARC_MAX_BODIES];
-    rot[0] = exp_map_to_quat_lib(ld3(root_exp + 3 * (size_t)i));
+    rot[0] = em_to_quat(ld3(root_exp + 3 * (size_t)i));
     pos[0] = ld3(root_pos + 3 * (size_t)i);
     st4(root_quat + 4 * (size_t)i, rot[0]);
     const float *d = dof + (size_t)i * m.dof_size;
@@ -105,7 +58,7 @@ __global__ __launch_bounds__(64) void pose_chain_bwd_kernel(parc_char_model_t m,
     const float *d = dof + (size_t)i * m.dof_size;
     float *gd = g_dof + (size_t)i * m.dof_size;
     for (int k = 0; k < m.dof_size; ++k) gd[k] = 0.f;
-    rot[0] = exp_map_to_quat_lib(em);
+    rot[0] = em_to_quat(em);
     for (int b = 1; b < B; ++b) {
         jq[b] = joint_dof_to_rot<true>(m, b, d, 1);
         loc[b] = quat_mul(mk4(m.local_rotation[b][0], m.local_rotation[b][1], m.local_rotation[b][2], m.local_rotation[b][3]), jq[b]);
@@ -119,7 +72,7 @@ __global__ __launch_bounds__(64) void pose_chain_bwd_kernel(parc_char_model_t m,
         const int p = m.parent[b];
         // pos[b] = pos[p] + rotate(rot[p], t_b)
         gpos[p] = gpos[p] + gpos[b];
-        grot[p] = qadd(grot[p], quat_rotate_bwd_q(rot[p], mk3(m.local_translation[b][0], m.local_translation[b][1], m.local_translation[b][2]), gpos[b]));
+        grot[p] = qadd(grot[p], qrot_bwd_q(rot[p], mk3(m.local_translation[b][0], m.local_translation[b][1], m.local_translation[b][2]), gpos[b]));
         // rot[b] = rot[p] (x) loc[b]
         grot[p] = qadd(grot[p], quat_mul(grot[b], quat_conj(loc[b])));
         const q4 gloc = quat_mul(quat_conj(rot[p]), grot[b]);
@@ -129,16 +82,16 @@ __global__ __launch_bounds__(64) void pose_chain_bwd_kernel(parc_char_model_t m,
         const int jt = m.joint_type[b], d0 = m.dof_idx[b];
         if (jt == PARC_JOINT_HINGE) {
             const v3 ax = mk3(m.joint_axis[b][0], m.joint_axis[b][1], m.joint_axis[b][2]);
-            gd[d0] = axis_angle_to_quat_bwd(ax, d[d0], jq[b], gj).g_angle;
+            gd[d0] = aa_to_quat_bwd(ax, d[d0], jq[b], gj).g_angle;
         } else if (jt == PARC_JOINT_SPHERICAL) {
-            const v3 ge = exp_map_to_quat_bwd(mk3(d[d0], d[d0 + 1], d[d0 + 2]), jq[b], gj);
+            const v3 ge = em_to_quat_bwd(mk3(d[d0], d[d0 + 1], d[d0 + 2]), jq[b], gj);
             gd[d0] = ge.x;
             gd[d0 + 1] = ge.y;
             gd[d0 + 2] = ge.z;
         }
     }
     st3(g_root_pos + 3 * (size_t)i, gpos[0]);
-    st3(g_root_exp + 3 * (size_t)i, exp_map_to_quat_bwd(em, rot[0], qadd(grot[0], ld4(g_root_quat + 4 * (size_t)i))));
+    st3(g_root_exp + 3 * (size_t)i, em_to_quat_bwd(em, rot[0], qadd(grot[0], ld4(g_root_quat + 4 * (size_t)i))));
 }
 
 // Angle between two rotations, torch_util.quat_diff_angle(q0, q1) = angle of q1 (x) conj(q0) (util/torch_util.py:421-431,68-88: the
@@ -147,9 +100,7 @@ __global__ __launch_bounds__(64) void pose_chain_bwd_kernel(parc_char_model_t m,
 __global__ __launch_bounds__(256) void quat_diff_angle_kernel(size_t n, const float *__restrict__ q0, const float *__restrict__ q1, float *angle) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const q4 d = quat_mul(ld4(q1 + 4 * i), quat_conj(ld4(q0 + 4 * i)));
-    const float s = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
-    angle[i] = s > 1e-5f ? 2.0f * atan2f(s, fabsf(d.w)) : 0.f;
+    angle[i] = qangle(quat_mul(ld4(q1 + 4 * i), quat_conj(ld4(q0 + 4 * i))));      // qdiff_angle on the FMA-grouped product
 }
 
 __global__ __launch_bounds__(256) void quat_diff_angle_grad_kernel(size_t n, const float *__restrict__ q0, const float *__restrict__ q1,
@@ -158,15 +109,12 @@ __global__ __launch_bounds__(256) void quat_diff_angle_grad_kernel(size_t n, con
     if (i >= n) return;
     const q4 a = ld4(q0 + 4 * i), b = ld4(q1 + 4 * i);
     const q4 d = quat_mul(b, quat_conj(a));
-    const float s = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
     q4 ga = mk4(0.f, 0.f, 0.f, 0.f), gb = ga;
-    if (s > 1e-5f) {
-        const float sg = d.w < 0.f ? -1.0f : 1.0f;           // quat_pos: the representative with w >= 0
-        const float w = sg * d.w, den = s * s + w * w, g = g_angle[i];
-        const float gs = 2.0f * w / den * g / s;               // d angle / d|v| * (v / |v|), on the flipped vector part ...
-        const q4 gd = q4{sg * gs * (sg * d.x), sg * gs * (sg * d.y), sg * gs * (sg * d.z), sg * (-2.0f * s / den * g)};     // ... and flipped back
-        gb = quat_mul(gd, a);                                   // d = b (x) conj(a):  g_b = g_d (x) a
-        const q4 gc = quat_mul(quat_conj(b), gd);               //                     g_conj(a) = conj(b) (x) g_d
+    if (sqrtf((d.x * d.x + d.y * d.y) + d.z * d.z) > 1e-5f) {      // in qangle's zero branch both stay exact zeros, not products with 0
+        // qangle_bwd has gs * d.x for the flip, scale, flip back sg * gs * (sg * d.x): multiplying by sg = +-1 is exact, the bits are the same
+        const q4 gd = qangle_bwd(d, g_angle[i]);
+        gb = quat_mul(gd, a);                                   // qdiff_bwd_b and qdiff_bwd_a on the FMA-grouped product, as d above
+        const q4 gc = quat_mul(quat_conj(b), gd);
         ga = q4{-gc.x, -gc.y, -gc.z, gc.w};
     }
     st4(g_q0 + 4 * i, ga);
@@ -269,7 +217,7 @@ __global__ __launch_bounds__(256) void body_points_world_grad_kernel(int n_frame
     for (int p = start[b]; p < start[b + 1]; ++p) {
         const v3 g = ld3(g_world + ((size_t)t * P + p) * 3);
         gp = gp + g;
-        gq = qadd(gq, quat_rotate_bwd_q(q, ld3(local + 3 * (size_t)p), g));
+        gq = qadd(gq, qrot_bwd_q(q, ld3(local + 3 * (size_t)p), g));
     }
     st3(g_body_pos + i * 3, gp);
     st4(g_body_rot + i * 4, gq);

@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/parc_render.h"
+#include "parc_rot.h"       // v3, q4, their operators, ld3/ld4, qmul, qrot
 
 #if defined(__HIPCC__)
 #define PARC_RHD __host__ __device__ __forceinline__
@@ -25,34 +26,11 @@
 
 namespace parc_rc {
 
-struct V3 {
-    float x, y, z;
-};
-PARC_RHD V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-PARC_RHD V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-PARC_RHD V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-PARC_RHD V3 operator*(float s, V3 a) { return V3{s * a.x, s * a.y, s * a.z}; }
-PARC_RHD float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-PARC_RHD V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-PARC_RHD V3 ld3(const float *p) { return V3{p[0], p[1], p[2]}; }
-PARC_RHD V3 normalize_or(V3 a, V3 fallback) {
-    const float l2 = dot(a, a);
+PARC_RHD v3 normalize_or(v3 a, v3 fallback) {
+    const float l2 = dot3(a, a);
     return (l2 > 1e-20f && l2 < 1e30f) ? (1.0f / sqrtf(l2)) * a : fallback;       // (NaN fails both comparisons)
 }
-struct Q4 {
-    float x, y, z, w;
-};
-PARC_RHD Q4 ld4(const float *p) { return Q4{p[0], p[1], p[2], p[3]}; }
-PARC_RHD Q4 qmul(Q4 a, Q4 b) {
-    return Q4{a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-              a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-PARC_RHD V3 qrot(Q4 q, V3 v) {        // v + w t + u x t, t = 2 u x v
-    const V3 u = v3(q.x, q.y, q.z);
-    const V3 t = 2.0f * cross(u, v);
-    return v + q.w * t + cross(u, t);
-}
-PARC_RHD V3 qrot_inv(Q4 q, V3 v) { return qrot(Q4{-q.x, -q.y, -q.z, q.w}, v); }
+PARC_RHD v3 qrot_inv(q4 q, v3 v) { return qrot(qconj(q), v); }
 // float -> index in [0, hi]; NaN -> 0 (fmaxf returns the other operand)
 PARC_RHD int clamp_index(float f, int hi) { return (int)fminf(fmaxf(f, 0.0f), (float)hi); }
 
@@ -67,7 +45,7 @@ struct WPrim {
 };
 
 struct Camera {
-    V3 eye, fwd, right, up;
+    v3 eye, fwd, right, up;
     float tan_half, aspect;
 };
 
@@ -76,19 +54,19 @@ struct Frame {
     Camera cam;
     const WPrim *prims;      // n_char[0] rows of the simulated character, then n_char[1] of the reference character
     int32_t n_char[2];
-    V3 bound_c[2];           // one bounding sphere per character
+    v3 bound_c[2];           // one bounding sphere per character
     float bound_r[2];
     parc_terrain_t ter;
-    V3 light;
+    v3 light;
     float ambient;
-    V3 color[2];
+    v3 color[2];
     int32_t shadows, num_bodies;
 };
 
 struct Hit {
     float t;
     int32_t id, tint;
-    V3 n;
+    v3 n;
 };
 
 // ---------------------------------------------------------------------------------------------- staging (once per view)
@@ -97,53 +75,53 @@ PARC_RHD int view_env(const parc_render_view_t &v, int n_envs) { return v.env < 
 PARC_RHD void camera_setup(const parc_render_view_t &v, const float *root_state, const float *env_offsets, int n_envs, int width, int height,
                            Camera &cam) {
     const int e = view_env(v, n_envs);
-    V3 eye = ld3(v.vec), tar = ld3(v.target);
+    v3 eye = ld3(v.vec), tar = ld3(v.target);
     if (v.mode == PARC_RENDER_CAM_TRACK) {
         const float rx = root_state[13 * (size_t)e] + env_offsets[3 * (size_t)e], ry = root_state[13 * (size_t)e + 1] + env_offsets[3 * (size_t)e + 1];
-        eye = v3(rx + v.vec[0], ry + v.vec[1], v.vec[2]);
-        tar = v3(rx, ry, 1.0f);
+        eye = mk3(rx + v.vec[0], ry + v.vec[1], v.vec[2]);
+        tar = mk3(rx, ry, 1.0f);
     }
     cam.eye = eye;
-    cam.fwd = normalize_or(tar - eye, v3(0.f, 1.f, 0.f));
-    V3 r = cross(cam.fwd, v3(0.f, 0.f, 1.f));
-    if (!(dot(r, r) > 1e-6f)) r = cross(cam.fwd, v3(0.f, 1.f, 0.f));        // looking along z: image up = world +y
-    cam.right = normalize_or(r, v3(1.f, 0.f, 0.f));
-    cam.up = cross(cam.right, cam.fwd);
+    cam.fwd = normalize_or(tar - eye, mk3(0.f, 1.f, 0.f));
+    v3 r = cross3(cam.fwd, mk3(0.f, 0.f, 1.f));
+    if (!(dot3(r, r) > 1e-6f)) r = cross3(cam.fwd, mk3(0.f, 1.f, 0.f));        // looking along z: image up = world +y
+    cam.right = normalize_or(r, mk3(1.f, 0.f, 0.f));
+    cam.up = cross3(cam.right, cam.fwd);
     const float fov = fminf(fmaxf(v.fov_y, 0.02f), 3.1f);                   // (NaN -> 0.02)
     cam.tan_half = tanf(0.5f * fov);
     cam.aspect = (float)width / (float)height;
 }
 
 // prim (body frame) -> world, for body pose (pos, rot) and a translation (env offset, + ref_char_offset for the reference character)
-PARC_RHD void prim_to_world(const parc_render_prim_t &p, V3 pos, Q4 rot, V3 shift, int id, int tint, WPrim &w) {
+PARC_RHD void prim_to_world(const parc_render_prim_t &p, v3 pos, q4 rot, v3 shift, int id, int tint, WPrim &w) {
     w.type = p.type;
     w.id = id;
     w.tint = tint;
-    const V3 a = pos + qrot(rot, ld3(p.a)) + shift;
+    const v3 a = pos + qrot(rot, ld3(p.a)) + shift;
     w.a[0] = a.x; w.a[1] = a.y; w.a[2] = a.z;
     w.radius = p.radius;
     if (p.type == PARC_RENDER_CAPSULE) {
-        const V3 b = pos + qrot(rot, ld3(p.b)) + shift;
+        const v3 b = pos + qrot(rot, ld3(p.b)) + shift;
         w.b[0] = b.x; w.b[1] = b.y; w.b[2] = b.z;
     } else {
         w.b[0] = p.b[0]; w.b[1] = p.b[1]; w.b[2] = p.b[2];
     }
-    const Q4 q = qmul(rot, ld4(p.q));
+    const q4 q = qmul(rot, ld4(p.q));
     w.q[0] = q.x; w.q[1] = q.y; w.q[2] = q.z; w.q[3] = q.w;
     w._pad[0] = w._pad[1] = 0.f;
 }
 
 // radius of the sphere around c that holds the n primitives
-PARC_RHD float bound_radius(const WPrim *w, int n, V3 c) {
+PARC_RHD float bound_radius(const WPrim *w, int n, v3 c) {
     float r = 0.f;
     for (int k = 0; k < n; ++k) {
-        const V3 a = ld3(w[k].a) - c;
-        float rk = sqrtf(dot(a, a));
+        const v3 a = ld3(w[k].a) - c;
+        float rk = sqrtf(dot3(a, a));
         if (w[k].type == PARC_RENDER_CAPSULE) {
-            const V3 b = ld3(w[k].b) - c;
-            rk = fmaxf(rk, sqrtf(dot(b, b))) + w[k].radius;
+            const v3 b = ld3(w[k].b) - c;
+            rk = fmaxf(rk, sqrtf(dot3(b, b))) + w[k].radius;
         } else if (w[k].type == PARC_RENDER_BOX) {
-            rk += sqrtf(dot(ld3(w[k].b), ld3(w[k].b)));
+            rk += sqrtf(dot3(ld3(w[k].b), ld3(w[k].b)));
         } else {
             rk += w[k].radius;
         }
@@ -167,12 +145,12 @@ PARC_RHD void stage_prim(int k, const parc_render_scene_t &sc, const Inputs &in,
     const parc_render_prim_t p = sc.prims[k - c * n];
     const int b = p.body < 0 ? 0 : (p.body >= B ? B - 1 : p.body);
     const size_t row = (size_t)e * B + b;
-    const V3 off = ld3(in.env_offsets + 3 * (size_t)e);
+    const v3 off = ld3(in.env_offsets + 3 * (size_t)e);
     if (c == 0) {
         int tint = 0;
         if (sc.show_contacts) {
-            const V3 cf = ld3(in.contact_forces + 3 * row);
-            tint = dot(cf, cf) > sc.contact_eps * sc.contact_eps;
+            const v3 cf = ld3(in.contact_forces + 3 * row);
+            tint = dot3(cf, cf) > sc.contact_eps * sc.contact_eps;
         }
         prim_to_world(p, ld3(in.rigid_body_state + 13 * row), ld4(in.rigid_body_state + 13 * row + 3), off, b, tint, wp[k]);
     } else {
@@ -188,7 +166,7 @@ PARC_RHD void stage_frame(const parc_render_view_t &view, const parc_terrain_t &
     fr.n_char[0] = sc.n_prims;
     fr.n_char[1] = in.ref_body_pos ? sc.n_prims : 0;
     fr.ter = ter;
-    fr.light = normalize_or(ld3(sc.light_dir), v3(0.f, 0.f, 1.f));
+    fr.light = normalize_or(ld3(sc.light_dir), mk3(0.f, 0.f, 1.f));
     fr.ambient = sc.ambient;
     fr.color[0] = ld3(sc.sim_color);
     fr.color[1] = ld3(sc.ref_color);
@@ -200,16 +178,16 @@ PARC_RHD void stage_frame(const parc_render_view_t &view, const parc_terrain_t &
 PARC_RHD void stage_bound(int c, const parc_render_scene_t &sc, const Inputs &in, int e, const WPrim *wp, Frame &fr) {
     const size_t row = (size_t)e * sc.num_bodies;
     const bool has_ref = in.ref_body_pos != nullptr;
-    const V3 off = ld3(in.env_offsets + 3 * (size_t)e);
-    const V3 cen = c == 0 ? ld3(in.rigid_body_state + 13 * row) + off : (has_ref ? ld3(in.ref_body_pos + 3 * row) + off + ld3(sc.ref_char_offset) : off);
+    const v3 off = ld3(in.env_offsets + 3 * (size_t)e);
+    const v3 cen = c == 0 ? ld3(in.rigid_body_state + 13 * row) + off : (has_ref ? ld3(in.ref_body_pos + 3 * row) + off + ld3(sc.ref_char_offset) : off);
     fr.bound_c[c] = cen;
     fr.bound_r[c] = bound_radius(wp + c * sc.n_prims, c == 0 || has_ref ? sc.n_prims : 0, cen);
 }
 
 // ---------------------------------------------------------------------------------------------- primitives
-PARC_RHD bool hit_sphere(V3 o, V3 d, V3 c, float r, float &t, V3 &n) {
-    const V3 oc = o - c;
-    const float b = dot(oc, d), cc = dot(oc, oc) - r * r;
+PARC_RHD bool hit_sphere(v3 o, v3 d, v3 c, float r, float &t, v3 &n) {
+    const v3 oc = o - c;
+    const float b = dot3(oc, d), cc = dot3(oc, oc) - r * r;
     const float h = b * b - cc;
     if (!(h > 0.f)) return false;
     const float tt = -b - sqrtf(h);
@@ -219,17 +197,17 @@ PARC_RHD bool hit_sphere(V3 o, V3 d, V3 c, float r, float &t, V3 &n) {
     return true;
 }
 
-PARC_RHD bool hit_capsule(V3 o, V3 d, V3 pa, V3 pb, float r, float &t, V3 &n) {
+PARC_RHD bool hit_capsule(v3 o, v3 d, v3 pa, v3 pb, float r, float &t, v3 &n) {
     bool any = false;
     float tb = kInf;
-    V3 nb = v3(0.f, 0.f, 1.f);
+    v3 nb = mk3(0.f, 0.f, 1.f);
     float tk;
-    V3 nk;
+    v3 nk;
     if (hit_sphere(o, d, pa, r, tk, nk)) { any = true; tb = tk; nb = nk; }
     if (hit_sphere(o, d, pb, r, tk, nk) && tk < tb) { any = true; tb = tk; nb = nk; }
     // the side: |oa + t d - ((oa + t d).ba / ba.ba) ba|^2 = r^2, kept where the foot point lies strictly between the ends
-    const V3 ba = pb - pa, oa = o - pa;
-    const float baba = dot(ba, ba), bard = dot(ba, d), baoa = dot(ba, oa), rdoa = dot(d, oa), oaoa = dot(oa, oa);
+    const v3 ba = pb - pa, oa = o - pa;
+    const float baba = dot3(ba, ba), bard = dot3(ba, d), baoa = dot3(ba, oa), rdoa = dot3(d, oa), oaoa = dot3(oa, oa);
     const float a = baba - bard * bard, b = baba * rdoa - baoa * bard, c = baba * oaoa - baoa * baoa - r * r * baba;
     const float h = b * b - a * c;
     if (a > 1e-12f * baba && h > 0.f) {
@@ -246,8 +224,8 @@ PARC_RHD bool hit_capsule(V3 o, V3 d, V3 pa, V3 pb, float r, float &t, V3 &n) {
     return any;
 }
 
-PARC_RHD bool hit_box(V3 o, V3 d, V3 c, V3 half, Q4 q, float &t, V3 &n) {
-    const V3 ol = qrot_inv(q, o - c), dl = qrot_inv(q, d);
+PARC_RHD bool hit_box(v3 o, v3 d, v3 c, v3 half, q4 q, float &t, v3 &n) {
+    const v3 ol = qrot_inv(q, o - c), dl = qrot_inv(q, d);
     const float oo[3] = {ol.x, ol.y, ol.z}, dd[3] = {dl.x, dl.y, dl.z}, hh[3] = {half.x, half.y, half.z};
     float tn = -kInf, tf = kInf, sgn = 0.f;
     int ax = 0;
@@ -265,11 +243,11 @@ PARC_RHD bool hit_box(V3 o, V3 d, V3 c, V3 half, Q4 q, float &t, V3 &n) {
     }
     if (!(tn < tf) || !(tn > 0.f)) return false;
     t = tn;
-    n = qrot(q, v3(ax == 0 ? sgn : 0.f, ax == 1 ? sgn : 0.f, ax == 2 ? sgn : 0.f));
+    n = qrot(q, mk3(ax == 0 ? sgn : 0.f, ax == 1 ? sgn : 0.f, ax == 2 ? sgn : 0.f));
     return true;
 }
 
-PARC_RHD bool hit_prim(const WPrim &w, V3 o, V3 d, float &t, V3 &n) {
+PARC_RHD bool hit_prim(const WPrim &w, v3 o, v3 d, float &t, v3 &n) {
     if (w.type == PARC_RENDER_SPHERE) return hit_sphere(o, d, ld3(w.a), w.radius, t, n);
     if (w.type == PARC_RENDER_CAPSULE) return hit_capsule(o, d, ld3(w.a), ld3(w.b), w.radius, t, n);
     if (w.type == PARC_RENDER_BOX) return hit_box(o, d, ld3(w.a), ld3(w.b), ld4(w.q), t, n);
@@ -277,22 +255,22 @@ PARC_RHD bool hit_prim(const WPrim &w, V3 o, V3 d, float &t, V3 &n) {
 }
 
 // does the ray meet the sphere at all (t >= 0), or start inside it?
-PARC_RHD bool touches_sphere(V3 o, V3 d, V3 c, float r) {
-    const V3 oc = o - c;
-    const float b = dot(oc, d), cc = dot(oc, oc) - r * r;
+PARC_RHD bool touches_sphere(v3 o, v3 d, v3 c, float r) {
+    const v3 oc = o - c;
+    const float b = dot3(oc, d), cc = dot3(oc, oc) - r * r;
     if (cc <= 0.f) return true;
     return b < 0.f && b * b - cc >= 0.f;
 }
 
 // nearest entry into a primitive of either character closer than hit.t
-PARC_RHD void trace_chars(const Frame &f, V3 o, V3 d, Hit &hit) {
+PARC_RHD void trace_chars(const Frame &f, v3 o, v3 d, Hit &hit) {
     int k0 = 0;
     for (int c = 0; c < 2; ++c) {
         const int n = f.n_char[c];
         if (n > 0 && touches_sphere(o, d, f.bound_c[c], f.bound_r[c])) {
             for (int k = k0; k < k0 + n; ++k) {
                 float t;
-                V3 nn;
+                v3 nn;
                 if (hit_prim(f.prims[k], o, d, t, nn) && t < hit.t) {
                     hit.t = t;
                     hit.n = nn;
@@ -307,7 +285,7 @@ PARC_RHD void trace_chars(const Frame &f, V3 o, V3 d, Hit &hit) {
 
 // ---------------------------------------------------------------------------------------------- terrain
 // 2-D DDA over the cells.  At most dim_x + dim_y + 2 steps; every index is clamped before the load.
-PARC_RHD void trace_terrain(const parc_terrain_t &ter, int id_base, V3 o, V3 d, Hit &hit) {
+PARC_RHD void trace_terrain(const parc_terrain_t &ter, int id_base, v3 o, v3 d, Hit &hit) {
     const int nx = ter.dim_x, ny = ter.dim_y;
     const float ou = (o.x - ter.min_x) / ter.dx + 0.5f, ov = (o.y - ter.min_y) / ter.dy + 0.5f;
     const float du = d.x / ter.dx, dv = d.y / ter.dy;
@@ -351,7 +329,7 @@ PARC_RHD void trace_terrain(const parc_terrain_t &ter, int id_base, V3 o, V3 d, 
                     hit.t = t_in;
                     hit.id = id_base + ci * ny + cj;
                     hit.tint = 0;
-                    hit.n = axis == 0 ? v3((float)-su, 0.f, 0.f) : v3(0.f, (float)-sv, 0.f);
+                    hit.n = axis == 0 ? mk3((float)-su, 0.f, 0.f) : mk3(0.f, (float)-sv, 0.f);
                 }
                 return;
             }
@@ -368,7 +346,7 @@ PARC_RHD void trace_terrain(const parc_terrain_t &ter, int id_base, V3 o, V3 d, 
                     hit.t = tt;
                     hit.id = id_base + ci * ny + cj;
                     hit.tint = 0;
-                    hit.n = v3(0.f, 0.f, 1.f);
+                    hit.n = mk3(0.f, 0.f, 1.f);
                 }
                 return;
             }
@@ -380,23 +358,23 @@ PARC_RHD void trace_terrain(const parc_terrain_t &ter, int id_base, V3 o, V3 d, 
     }
 }
 
-PARC_RHD void trace(const Frame &f, V3 o, V3 d, Hit &hit) {
+PARC_RHD void trace(const Frame &f, v3 o, v3 d, Hit &hit) {
     hit.t = kInf;
     hit.id = -1;
     hit.tint = 0;
-    hit.n = v3(0.f, 0.f, 1.f);
+    hit.n = mk3(0.f, 0.f, 1.f);
     trace_chars(f, o, d, hit);
     trace_terrain(f.ter, 2 * f.num_bodies, o, d, hit);
 }
 
 // ---------------------------------------------------------------------------------------------- one pixel
-PARC_RHD uint32_t pack_rgba(V3 c) {
+PARC_RHD uint32_t pack_rgba(v3 c) {
     const uint32_t r = (uint32_t)(fminf(fmaxf(c.x, 0.f), 1.f) * 255.f + 0.5f), g = (uint32_t)(fminf(fmaxf(c.y, 0.f), 1.f) * 255.f + 0.5f),
                    b = (uint32_t)(fminf(fmaxf(c.z, 0.f), 1.f) * 255.f + 0.5f);
     return r | (g << 8) | (b << 16) | 0xFF000000u;
 }
 
-PARC_RHD V3 pixel_ray(const Camera &cam, int px, int py, int width, int height) {
+PARC_RHD v3 pixel_ray(const Camera &cam, int px, int py, int width, int height) {
     const float sx = (2.0f * ((float)px + 0.5f) / (float)width - 1.0f) * cam.tan_half * cam.aspect;
     const float sy = (1.0f - 2.0f * ((float)py + 0.5f) / (float)height) * cam.tan_half;
     return normalize_or(cam.fwd + sx * cam.right + sy * cam.up, cam.fwd);
@@ -404,29 +382,29 @@ PARC_RHD V3 pixel_ray(const Camera &cam, int px, int py, int width, int height) 
 
 // normal_out (3 floats, optional): the shading normal, for the host tests
 PARC_RHD void shade_pixel(const Frame &f, int px, int py, int width, int height, uint32_t &rgba, float &depth, int32_t &id, float *normal_out) {
-    const V3 o = f.cam.eye, d = pixel_ray(f.cam, px, py, width, height);
+    const v3 o = f.cam.eye, d = pixel_ray(f.cam, px, py, width, height);
     Hit hit;
     trace(f, o, d, hit);
     depth = hit.t;
     id = hit.id;
     if (normal_out) { normal_out[0] = hit.n.x; normal_out[1] = hit.n.y; normal_out[2] = hit.n.z; }
     if (hit.id < 0) {
-        rgba = pack_rgba(v3(0.62f, 0.74f, 0.90f));     // sky
+        rgba = pack_rgba(mk3(0.62f, 0.74f, 0.90f));     // sky
         return;
     }
-    V3 albedo;
+    v3 albedo;
     const int B = f.num_bodies;
     if (hit.id < 2 * B) {
         albedo = f.color[hit.id < B ? 0 : 1];
-        if (hit.tint) albedo = 0.4f * albedo + v3(0.6f, 0.06f, 0.03f);
+        if (hit.tint) albedo = 0.4f * albedo + mk3(0.6f, 0.06f, 0.03f);
     } else {
         const int cell = hit.id - 2 * B, ci = cell / f.ter.dim_y, cj = cell - ci * f.ter.dim_y;
         const float h = f.ter.hf[(size_t)ci * f.ter.dim_y + cj];        // (ci, cj were clamped when the id was made)
         const float k = fminf(fmaxf(0.5f + 0.25f * h, 0.f), 1.f);       // tint by height ...
-        albedo = v3(0.45f + 0.35f * k, 0.55f + 0.10f * k, 0.42f - 0.12f * k);
+        albedo = mk3(0.45f + 0.35f * k, 0.55f + 0.10f * k, 0.42f - 0.12f * k);
         if ((ci + cj) & 1) albedo = 0.85f * albedo;                     // ... and a checker by cell parity
     }
-    float diffuse = fmaxf(dot(hit.n, f.light), 0.f);
+    float diffuse = fmaxf(dot3(hit.n, f.light), 0.f);
     if (f.shadows && diffuse > 0.f) {
         Hit sh;
         trace(f, o + hit.t * d + kShadowBias * hit.n, f.light, sh);

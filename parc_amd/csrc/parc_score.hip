@@ -42,7 +42,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void motion_score_frames_kernel(
     v3 pos;
     q4 rot;
     group_fk(m, lane, ld3(root_pos + 3 * row), ld4(root_rot + 4 * row), jq, pos, rot);
-    int bad = lane < Bd && !finite_pose(V3{pos.x, pos.y, pos.z}, Q4{rot.x, rot.y, rot.z, rot.w});
+    int bad = lane < Bd && !finite_pose(pos, rot);
     if (body_pos_ws && lane < Bd) st3(body_pos_ws + (row * Bd + lane) * 3, pos);
 
     const Field fld = make_field(ter, base_z);
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void motion_score_frames_kernel(
         const q4 br = shfl16(rot, b);
         int p0, p1;
         body_range(start, b, n_points, p0, p1);
-        const float mn = min16(body_lane_terms(fld, V3{bp.x, bp.y, bp.z}, Q4{br.x, br.y, br.z, br.w}, local, p0, p1, lane, pen_acc, bad));
+        const float mn = min16(body_lane_terms(fld, bp, br, local, p0, p1, lane, pen_acc, bad));
         if (lane == b && p1 > p0) con = contacts[row * Bd + b] * mn;
     }
     const float pen_f = sum16(pen_acc), con_f = sum16(con);

@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "../../include/parc_score.h"
+#include "parc_rot.h"       // v3, q4, qrot
 #include "parc_sdf_core.h"
 
 #if defined(__HIPCC__)
@@ -23,24 +24,9 @@ namespace parc_sc {
 constexpr int kLanes = 16;          // lanes of a frame group (= PARC_MAX_BODIES: lane b holds body b)
 constexpr int kFoldThreads = 64;    // threads of the per-candidate fold
 
-struct V3 {
-    float x, y, z;
-};
-struct Q4 {
-    float x, y, z, w;
-};
-PARC_SC_FN V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-// util/torch_util.py:60-66, the operation order of quat_rotate (parc_math.h)
-PARC_SC_FN V3 qrot(Q4 q, V3 v) {
-    const V3 u = V3{q.x, q.y, q.z};
-    const V3 c0 = cross(u, v);
-    const V3 t = V3{2.f * c0.x, 2.f * c0.y, 2.f * c0.z};
-    const V3 c = cross(u, t);
-    return V3{v.x + q.w * t.x + c.x, v.y + q.w * t.y + c.y, v.z + q.w * t.z + c.z};
-}
 // false for NaN and for +-inf
 PARC_SC_FN bool finite1(float x) { return fabsf(x) <= 3.4028234663852886e38f; }
-PARC_SC_FN bool finite_pose(V3 p, Q4 q) {
+PARC_SC_FN bool finite_pose(v3 p, q4 q) {
     return finite1(p.x) && finite1(p.y) && finite1(p.z) && finite1(q.x) && finite1(q.y) && finite1(q.z) && finite1(q.w);
 }
 
@@ -53,8 +39,8 @@ PARC_SC_FN Field make_field(const parc_score_terrain_t &t, float base_z) { retur
 
 // One sample point: pen = -min(sdf_inverted, 0) = max(min over the air columns, 0), d_out = max(min over the ground columns, 0).
 // fmaxf drops NaNs, so a non-finite world position raises `bad` instead.
-PARC_SC_FN void point_terms(const Field &f, V3 pos, Q4 rot, const float *local, float &pen, float &d_out, int &bad) {
-    const V3 r = qrot(rot, V3{local[0], local[1], local[2]});
+PARC_SC_FN void point_terms(const Field &f, v3 pos, q4 rot, const float *local, float &pen, float &d_out, int &bad) {
+    const v3 r = qrot(rot, ld3(local));
     const float px = pos.x + r.x, py = pos.y + r.y, pz = pos.z + r.z;
     if (!(finite1(px) && finite1(py) && finite1(pz))) {
         bad = 1;
@@ -73,7 +59,7 @@ PARC_SC_FN void point_terms(const Field &f, V3 pos, Q4 rot, const float *local, 
 
 // Lane `lane` of a frame group on body b (pose pos, rot; points p0 .. p1-1): the lane takes points p0 + lane, p0 + lane + 16, ...  Adds
 // their penetration to pen_acc in that order and returns the smallest d_out among them (+inf when the lane has none).
-PARC_SC_FN float body_lane_terms(const Field &f, V3 pos, Q4 rot, const float *local, int p0, int p1, int lane, float &pen_acc, int &bad) {
+PARC_SC_FN float body_lane_terms(const Field &f, v3 pos, q4 rot, const float *local, int p0, int p1, int lane, float &pen_acc, int &bad) {
     float lane_min = INFINITY;
     for (int p = p0 + lane; p < p1; p += kLanes) {
         float pen, d_out;
@@ -191,8 +177,8 @@ static inline void frame_terms_host(const Field &f, int num_bodies, const float 
     int bad = 0;
     for (int l = 0; l < kLanes; ++l) pen_acc[l] = con[l] = 0.f;
     for (int b = 0; b < num_bodies; ++b) {
-        const V3 pos = V3{body_pos[3 * b], body_pos[3 * b + 1], body_pos[3 * b + 2]};
-        const Q4 rot = Q4{body_rot[4 * b], body_rot[4 * b + 1], body_rot[4 * b + 2], body_rot[4 * b + 3]};
+        const v3 pos = ld3(body_pos + 3 * b);
+        const q4 rot = ld4(body_rot + 4 * b);
         if (!finite_pose(pos, rot)) bad = 1;
         int p0, p1;
         body_range(start, b, n_points, p0, p1);
