@@ -10,14 +10,18 @@
 
 #define PARC_DEV __device__ __forceinline__
 
-// ---- single-instruction / short-polynomial primitives (each within ~1-2 ulp of the correctly rounded value; the
-// library versions cost 10-200 instructions per call and the post-step kernel is VALU-issue bound) -----------------
+// ---- single-instruction / short-polynomial primitives (the library versions cost 10-200 instructions per call and the
+// post-step kernel is VALU-issue bound).  Their accuracy is not claimed here primitive by primitive: what is held is what the
+// kernels built on them return, at every branch point, within 4 e-bar of float64 (tests/test_kin_branch_gpu.py; the bounds are
+// tests/tools/kin_ref.py MEASURED_*, the reference's own fp32-versus-float64 error).  The figures quoted below come from a float32
+// emulation of the polynomials on a CPU; they are not device measurements. -----------------
 PARC_DEV float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
 PARC_DEV float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 PARC_DEV float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 
-// sin and cos of x, |x| up to a few hundred: k = rint(x * 2/pi), two-constant reduction by pi/2, degree-7/8
-// polynomials on [-pi/4, pi/4] (least-squares fits, |err| < 8e-8), quadrant fix-up
+// sin and cos of x: k = rint(x * 2/pi), two-constant reduction by pi/2, degree-7/8 polynomials on [-pi/4, pi/4] (least-squares
+// fits), quadrant fix-up.  CPU emulation: |err| about 9e-8 up to |x| = 1e5.  Through the kernels: hinge angles up to +-600 (x = 300
+// here) give joint quaternions within kin_ref.MEASURED_DOF_TO_ROT of float64 (test_dof_to_rot_at_its_branch_points).
 PARC_DEV void fsincos(float x, float &s, float &c) {
     float k = rintf(x * 0.63661977236758134f);
     float r = fmaf(k, -1.5707963705062866f, x);
@@ -34,7 +38,9 @@ PARC_DEV void fsincos(float x, float &s, float &c) {
     c = ((q + 1) & 2) ? -co : co;
 }
 
-// atan2(y, x) for y >= 0, x >= 0 (the only case the quaternion angle needs): odd degree-17 fit on [0, 1], |err| < 8e-8
+// atan2(y, x) for y >= 0, x >= 0 (the only case the quaternion angle needs): odd degree-17 fit on [0, 1].  CPU emulation: |err|
+// about 1.7e-7.  Through the kernels: dofs (twice this angle) within kin_ref.MEASURED_ROT_TO_DOF of float64, finite-difference
+// velocities within MEASURED_BUILD_VEL (test_rot_to_dof_at_its_branch_points, test_motion_lib_build_at_its_branch_points).
 PARC_DEV float fatan2_q1(float y, float x) {
     float mn = fminf(x, y), mx = fmaxf(x, y);
     float t = mn * frcp(mx);
@@ -52,7 +58,8 @@ PARC_DEV float fatan2_q1(float y, float x) {
     return y > x ? 1.5707963267948966f - a : a;
 }
 
-// acos(c) for 0 <= c <= 1: sqrt(1 - c) * P(c), degree-7 fit, relative error < 2.1e-7
+// acos(c) for 0 <= c <= 1: sqrt(1 - c) * P(c), degree-7 fit.  CPU emulation: relative error about 2.1e-7.  Through the kernels:
+// slerp within kin_ref.MEASURED_SLERP_DECADE of float64 per decade of sin(half angle) (test_calc_motion_frame_at_slerps_overrides).
 PARC_DEV float facos01(float c) {
     float p = fmaf(c, -0.0012370048789307475f, 0.006580885034054518f);
     p = fmaf(c, p, -0.01696547120809555f);

@@ -48,7 +48,8 @@ PARC_ROT_FN void st3(float *p, v3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
 PARC_ROT_FN void st4(float *p, q4 q) { p[0] = q.x; p[1] = q.y; p[2] = q.z; p[3] = q.w; }
 
 // ---- torch-order functions ----
-// util/torch_util.py:577-594 quat_multiply: the 16 products, summed left to right
+// util/torch_util.py:577-594 quat_multiply: the 16 products, summed left to right (quat_mul at :40-58, which the reference's
+// kinematics call, is the same product in a 9-multiplication grouping; parc_math.h's FMA-grouped quat_mul cites that one)
 PARC_ROT_FN q4 qmul(q4 a, q4 b) {
     return q4{((a.w * b.x + a.x * b.w) + a.y * b.z) - a.z * b.y, ((a.w * b.y - a.x * b.z) + a.y * b.w) + a.z * b.x,
               ((a.w * b.z + a.x * b.y) - a.y * b.x) + a.z * b.w, ((a.w * b.w - a.x * b.x) - a.y * b.y) - a.z * b.z};
