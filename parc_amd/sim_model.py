@@ -142,7 +142,12 @@ class SimModel:
         s.num_bodies, s.dof_size = B, D
         par = km._parent_indices.cpu().numpy()
         lt = km._local_translation.cpu().numpy()
-        lr = km._local_rotation.cpu().numpy()
+        lr = km._local_rotation.cpu().numpy().astype(np.float64)
+        # an MJCF quaternion written to a few digits is not unit, and the kernels build a link's frame with qmat(local_rotation * q), which
+        # takes a unit quaternion: off by 1.3e-4 it is no rotation, and body velocities come out 1e-3 wrong.  A quaternion
+        # that is unit to fp32 stays as it is, bit for bit.
+        nrm = np.linalg.norm(lr, axis=-1, keepdims=True)
+        lr = np.where(np.abs(nrm - 1.0) > 1e-6, lr / nrm, lr)
         self.body_mass = np.zeros(B)
         self.body_com = np.zeros((B, 3))
         self.body_inertia_com = np.zeros((B, 3, 3))

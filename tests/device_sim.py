@@ -52,12 +52,23 @@ class DeviceSim:
         self.rigid_body_state[:] = rb.cpu().numpy()
         self.contact_forces[:] = cf.cpu().numpy()
 
-    def refresh_bodies(self):
+    def refresh_bodies(self, env_ids=None, mask=None):
+        """All envs; or the envs of `env_ids` (the index-list entry); or the envs whose `mask` is set (parc_sim_refresh_bodies_masked).
+        The other rows of rigid_body_state / contact_forces go up and come back as they are."""
         m = self._model()
         rs, ds, rb, cf = self._up(self.root_state), self._up(self.dof_state), self._up(self.rigid_body_state), self._up(self.contact_forces)
         p = _hip.ptr
-        _hip.check(_hip.lib().parc_sim_refresh_bodies(_hip.stream(), _hip.c_vp(m.data_ptr()), self.n, None, 0, p(rs), p(ds), p(rb), p(cf)),
-                   "parc_sim_refresh_bodies")
+        if mask is not None:
+            assert env_ids is None and len(mask) == self.n
+            mk = torch.tensor(np.asarray(mask, np.int32), device=DEV)
+            _hip.check(_hip.lib().parc_sim_refresh_bodies_masked(_hip.stream(), _hip.c_vp(m.data_ptr()), self.n, p(mk), p(rs), p(ds), p(rb), p(cf)),
+                       "parc_sim_refresh_bodies_masked")
+        else:
+            ids = None if env_ids is None else torch.tensor(np.asarray(env_ids, np.int64), device=DEV)
+            assert ids is None or (ids.numel() > 0 and int(ids.min()) >= 0 and int(ids.max()) < self.n)
+            _hip.check(_hip.lib().parc_sim_refresh_bodies(_hip.stream(), _hip.c_vp(m.data_ptr()), self.n, p(ids) if ids is not None else None,
+                                                          0 if ids is None else int(ids.numel()), p(rs), p(ds), p(rb), p(cf)),
+                       "parc_sim_refresh_bodies")
         torch.cuda.synchronize()
         self.rigid_body_state[:] = rb.cpu().numpy()
         self.contact_forces[:] = cf.cpu().numpy()
